@@ -15,7 +15,13 @@ The eval leg is the fast-eval pipeline (Manager._eval_fast): the 72,024-row MIND
 table encoded (sharded over ranks + RCCL all-gather), batched predict_fast over a synthetic
 MIND-large-shaped dev split (376,471 impressions, ~37 candidates each), and cal_metric on the GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--data device|resident]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--data device|resident]
+                    [--full [--no-cpu-baseline] ...]
+
+A plain run sets up, warms up, times the K steps and prints the headline.  ``--full`` adds every other
+measurement beside it: the per-launch projection-GEMM roofline, the eval legs, XFormer, the other
+two-tower configurations, the standalone gather and the CPU baseline.  ``--dump-outputs DIR`` writes
+what the last timed step handed its caller (logits, loss) as DIR/<name>.npy.
 
 Rank 0 prints ONE JSON line.  N > 1: either launch with torch.distributed.run (one rank/GPU), or
 run ``bench.py --gpus N`` directly and it spawns the N ranks itself (twotower.py:62-73).
@@ -192,6 +198,7 @@ class GraphedStep:
 
 
 _ONES = {}
+LAST_STEP = {}   # the latest forward_backward's logits and loss (dump_outputs)
 
 
 def _one(t):
@@ -208,11 +215,14 @@ def forward_backward(model, opt, x):
     loss into their head: TwoTowerBaseModel.forward_loss)."""
     opt.zero_grad(set_to_none=True)
     if hasattr(model, "forward_loss"):
-        _, loss = model.forward_loss(x)
+        logits, loss = model.forward_loss(x)
     else:
         logits, _ = model(x)
         loss = torch.nn.functional.nll_loss(logits, x["label"])
     loss.backward(_one(loss))
+    # what the step hands its caller, kept for --dump-outputs (captured in a graph these are the
+    # replay's static outputs: every replay refreshes them)
+    LAST_STEP["logits"], LAST_STEP["loss"] = logits.detach(), loss.detach()
     return loss
 
 
@@ -495,6 +505,22 @@ def cpu_baseline(seconds=20.0):
             "eval_sample": "%d eval-mode forwards of B=32 x 5 candidates (sigmoid), oracle/restatement.py" % ne}
 
 
+def dump_outputs(path):
+    """What the last timed step handed its caller, as float32 ``path/<name>.npy``: ``logits`` ([B, C]
+    log-softmax scores) and ``loss`` ([1]), the pair ``forward_loss`` returns.  They come out of every
+    kernel of the step -- forward directly, backward and Adam through the parameters the earlier steps
+    left -- and repeat from run to run to a few ulp: initialisation, the synthetic split and the device
+    RNG streams are seeded, so the inputs are identical.  Gradients and updated parameters are NOT
+    written: the backward's atomic adds land in arrival order, a gradient that is zero in exact
+    arithmetic (the user tower's pooling query) is then rounding noise of either sign, and Adam's
+    g / sqrt(v) turns such noise into moves of a full lr per step -- arrays that differ between two
+    runs of one build by far more than rounding while the logits agree."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("logits", LAST_STEP["logits"]), ("loss", LAST_STEP["loss"].reshape(1))):
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -502,6 +528,11 @@ def main():
                          "spawns them itself (default 1, or WORLD_SIZE under torch.distributed.run)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the projection-GEMM roofline, the eval legs, XFormer, the other "
+                         "configurations, the gather and the CPU baseline (the options below tune these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--data", choices=["device", "resident"], default="device",
@@ -609,46 +640,52 @@ def main():
     if in_sync is not None and not in_sync["dp_in_sync"]:
         print("bench.py: ranks diverged after the timed steps: %s" % json.dumps(in_sync), file=sys.stderr)
 
-    # per-launch timing of the step's projection GEMMs: the launches of one eager step kept as
-    # closures over their real operands, each replayed back to back between HIP events on its stream
-    # (events cannot sit inside a graph replay; rocprofv3's trace of the graphed step agrees)
-    F.PROBE.enable()
-    feed.feed(a.steps)
-    train_step(model, opt, feed.form(), sync)
-    probe = F.PROBE.time(reps=20)
-    F.PROBE.disable()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs)
 
-    # eval (a): forward in eval mode (sigmoid) over train-shaped batches -> candidates scored/s
-    model.eval()
-    evb = []
-    for i in range(4):
-        feed.feed(i)
-        evb.append({k: v.clone() for k, v in feed.form().items()})
-    with torch.no_grad():
-        for i in range(3):
-            model(evb[i % len(evb)])
-        torch.cuda.synchronize()
-        ne = max(5, a.steps // 2)
-        t1 = time.perf_counter()
-        for i in range(ne):
-            model(evb[i % len(evb)])
-        torch.cuda.synchronize()
-        el_eval = time.perf_counter() - t1
-    del evb
+    probe, fast, xf, legs, gather, ne, el_eval = {}, None, None, None, None, 0, 0.0
+    if a.full:
+        # per-launch timing of the step's projection GEMMs: the launches of one eager step kept as
+        # closures over their real operands, each replayed back to back between HIP events on its stream
+        # (events cannot sit inside a graph replay; rocprofv3's trace of the graphed step agrees)
+        F.PROBE.enable()
+        feed.feed(a.steps)
+        train_step(model, opt, feed.form(), sync)
+        probe = F.PROBE.time(reps=20)
+        F.PROBE.disable()
+
+        # eval (a): forward in eval mode (sigmoid) over train-shaped batches -> candidates scored/s
+        model.eval()
+        evb = []
+        for i in range(4):
+            feed.feed(i)
+            evb.append({k: v.clone() for k, v in feed.form().items()})
+        with torch.no_grad():
+            for i in range(3):
+                model(evb[i % len(evb)])
+            torch.cuda.synchronize()
+            ne = max(5, a.steps // 2)
+            t1 = time.perf_counter()
+            for i in range(ne):
+                model(evb[i % len(evb)])
+            torch.cuda.synchronize()
+            el_eval = time.perf_counter() - t1
+        del evb
     if sync is not None:
         sync.close()   # the legs below install their own GradSync (the hooks are process-wide)
-    # eval (b): the fast-eval pipeline over a MIND-large-shaped dev split
-    fast = fast_eval_leg(model, dev, world, rank, a.eval_impr) if a.eval_impr > 0 else None
-    # configs[4] (XFormer) and configs[1]/[3] at every N: the 8-GPU configurations are measured on N ranks
-    xf = xformer_leg(dev, a.xformer_steps, world=world, rank=rank) if a.xformer_steps > 0 else None
-    only = [n for n in a.legs.split(",") if n] or None
-    legs = config_legs(dev, feed, world=world, only=only) if (a.config_legs and a.data == "device") else None
-    gather = gather_probe(dev) if world == 1 else None
+    if a.full:
+        # eval (b): the fast-eval pipeline over a MIND-large-shaped dev split
+        fast = fast_eval_leg(model, dev, world, rank, a.eval_impr) if a.eval_impr > 0 else None
+        # configs[4] (XFormer) and configs[1]/[3] at every N: the 8-GPU configurations are measured on N ranks
+        xf = xformer_leg(dev, a.xformer_steps, world=world, rank=rank) if a.xformer_steps > 0 else None
+        only = [n for n in a.legs.split(",") if n] or None
+        legs = config_legs(dev, feed, world=world, only=only) if (a.config_legs and a.data == "device") else None
+        gather = gather_probe(dev) if world == 1 else None
 
     if rank == 0:
         ms = el / a.steps * 1e3
         value = world * B * a.steps / el
-        from newsrec_amd import _lib as Lb, kernels as Kn
+        from newsrec_amd import _lib as Lb
         split = Kn.get_gemm_precision() == Lb.GEMM_BF16X6
         # bf16x6: six bf16 MFMAs per fp32 multiply-add -> fp32-equivalent peak = bf16 dense peak / 6
         peak = BF16_MFMA_PEAK_TF / 6 if split else FP32_MFMA_PEAK_TF
@@ -700,22 +737,25 @@ def main():
                        if a.data == "device" else "pre-formed synthetic batches resident in HBM",
                        "global_batch": B * world, "per_gpu_batch": B, "candidates": C, "history": NH,
                        "seq_len": L, "parallelism": "dp%d" % world},
-            "eval": dict(fast or {}, forward={"candidates_per_s": round(world * B * C * ne / el_eval, 1),
-                                              "impressions_per_s": round(world * B * ne / el_eval, 1),
-                                              "mode": "model(x) in eval mode (sigmoid) on train-shaped batches"}),
-            "roofline": {"kernel": "%s GEMM of the news-tower key/value projection (%s)"
-                                   % (dom, gd.get("what")) if dom else None, "bound": "mfma",
-                         "achieved": round(achieved, 2) if achieved else None, "peak": round(peak, 1),
-                         "unit": "TFLOP/s", "frac": round(achieved / peak, 4) if achieved else None,
-                         "peak_basis": ("fp32-equivalent: 2.5 PF bf16 dense MFMA / 6 (bf16x6 split arithmetic)"
-                                        if split else "fp32 MFMA (v_mfma_f32_32x32x2_f32)"),
-                         "frac_of_fp32_peak": round(achieved / FP32_MFMA_PEAK_TF, 4) if achieved else None,
-                         "traffic": traffic, "launch_ms": round(gemm_ms, 4) if gemm_ms else None,
-                         "flops_per_launch": gemm_flops, "rows_per_launch": gemm_rows,
-                         "tokens_per_launch": B * (C + NH) * L,
-                         "timing": "per-launch average of 20 replays of the step's own launch, each after a 512 MB cache-evicting write "
-                                   "(HIP events on its stream)", "projection_gemms": gemms},
+            "full": bool(a.full),
         }
+        if a.full:
+            out["eval"] = dict(fast or {}, forward={"candidates_per_s": round(world * B * C * ne / el_eval, 1),
+                                                    "impressions_per_s": round(world * B * ne / el_eval, 1),
+                                                    "mode": "model(x) in eval mode (sigmoid) on train-shaped batches"})
+            out["roofline"] = {
+                "kernel": "%s GEMM of the news-tower key/value projection (%s)"
+                          % (dom, gd.get("what")) if dom else None, "bound": "mfma",
+                "achieved": round(achieved, 2) if achieved else None, "peak": round(peak, 1),
+                "unit": "TFLOP/s", "frac": round(achieved / peak, 4) if achieved else None,
+                "peak_basis": ("fp32-equivalent: 2.5 PF bf16 dense MFMA / 6 (bf16x6 split arithmetic)"
+                               if split else "fp32 MFMA (v_mfma_f32_32x32x2_f32)"),
+                "frac_of_fp32_peak": round(achieved / FP32_MFMA_PEAK_TF, 4) if achieved else None,
+                "traffic": traffic, "launch_ms": round(gemm_ms, 4) if gemm_ms else None,
+                "flops_per_launch": gemm_flops, "rows_per_launch": gemm_rows,
+                "tokens_per_launch": B * (C + NH) * L,
+                "timing": "per-launch average of 20 replays of the step's own launch, each after a 512 MB cache-evicting write "
+                          "(HIP events on its stream)", "projection_gemms": gemms}
         if in_sync is not None:
             out.update(in_sync)
         if xf is not None:
@@ -724,7 +764,7 @@ def main():
             out["other_configs"] = legs
         if gather is not None:
             out["gather"] = gather
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(a.cpu_seconds)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -176,7 +176,7 @@ def test_bench_gpus2_spawns_two_ranks(shard):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["NR_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-           "--eval-impr", "0", "--legs", "cnn_lstur", "--xformer-steps", "2", "--no-cpu-baseline"] + \
+           "--full", "--eval-impr", "0", "--legs", "cnn_lstur", "--xformer-steps", "2", "--no-cpu-baseline"] + \
         (["--shard-table"] if shard else [])
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=580)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -8,7 +8,7 @@ echo tests base; timeout -k 10 600 python -u -m pytest $T -m gpu -x -q --timeout
 for v in $VARS; do
   echo tests $v; NR_LIB_PATH=$GRAFT_REPO_ROOT/ab/$v/libnewsrec_hip.so timeout -k 10 600 python -u -m pytest $T -m gpu -x -q --timeout 300 --timeout-method thread > $O/tests_$v.log 2>&1 || exit 1
 done
-B="python bench.py --steps 30 --warmup 20 --no-cpu-baseline --eval-impr 0 --config-legs 0 --xformer-steps 0"
+B="python bench.py --full --steps 30 --warmup 20 --no-cpu-baseline --eval-impr 0 --config-legs 0 --xformer-steps 0"
 for i in $(seq 1 $R); do
   echo round $i
   timeout -k 10 200 $B > $O/bench_base_$i.json 2>> $O/bench.err || exit 3

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/${1:-ab}; mkdir -p $O
 T=${2:-tests/test_news_encoder_gpu.py}
 echo tests; timeout -k 10 600 python -u -m pytest $T -m gpu -x -q --timeout 300 --timeout-method thread > $O/tests.log 2>&1 || exit 1
-B="python bench.py --steps 30 --warmup 20 --no-cpu-baseline --eval-impr 0 --config-legs 0 --xformer-steps 0"
+B="python bench.py --full --steps 30 --warmup 20 --no-cpu-baseline --eval-impr 0 --config-legs 0 --xformer-steps 0"
 for i in 1 2 3; do
   echo round $i
   timeout -k 10 200 $B > $O/bench_new_$i.json 2>> $O/bench.err || exit 3

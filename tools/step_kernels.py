@@ -1,6 +1,7 @@
 """Kernels of one train step in a rocprofv3 kernel trace (between two consecutive Adam launches), with
 durations.  python tools/step_kernels.py TRACE_DIR [BACK]: BACK = 1 (default) takes the last segment;
-bench.py's trace ends with its eager probe step, so BACK = 2 is its last graphed step."""
+a ``bench.py --full`` trace ends with its eager probe step, so BACK = 2 is its last graphed step (a plain
+run's trace ends with a graphed step: BACK = 1)."""
 import csv
 import sys
 
