@@ -3,8 +3,8 @@
 
 namespace nrfast {
 
-int launch_big_3_128(const Args& g, int am, int bm, int splits, hipStream_t s) {
-  return launch_big_modes<3, 128>(g, am, bm, splits, s);
+int launch_big_3_128(const Args& g, const GemmRoute& r, hipStream_t s) {
+  return launch_big_modes<3, 128>(g, r, s);
 }
 
 }  // namespace nrfast

@@ -610,54 +610,15 @@ __global__ __launch_bounds__(512, 1) void gemm_big_kernel(Args g) {
   }
 }
 
-template <typename Kern>
-int resident_slots_512(Kern k) {
-  static int cache[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
-  if (cache[dev] == 0) {
-    int cus = 0, per = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, 512, 0) != hipSuccess) return 0;
-    cache[dev] = cus * per;
-  }
-  return cache[dev];
-}
-
-template <int AM, int BMODE, bool TR, int NP, int BN>
-int launch_big(const Args& g, int splits, hipStream_t s) {
-  const int64_t gm = (g.M + BIG_BM - 1) / BIG_BM, gn = (g.N + BN - 1) / BN;
-  const int64_t units = gm * gn * splits;
-  if (units <= 0) return NR_OK;
-  if (units > 0x7fffffff) return NR_EINVAL(0);
-  int grid = (int)units;
-  const int slots = capped_slots(resident_slots_512(gemm_big_kernel<AM, BMODE, TR, NP, BN>), g.max_cus);
-  if (slots > 0 && slots < grid) grid = slots;
-  Args a = g;
-  a.splits = splits;
-  hipLaunchKernelGGL((gemm_big_kernel<AM, BMODE, TR, NP, BN>), dim3((unsigned)grid), dim3(512), 0, s, a);
-  NR_LAUNCH_CHECK();
-  return NR_OK;
-}
-
-// operand-mode dispatch of one (NP, BN); -1 = combination not instantiated
+// operand-mode dispatch of one (NP, BN)
 template <int NP, int BN>
-int launch_big_modes(const Args& g, int am, int bm, int splits, hipStream_t s) {
-  const bool atomic_epi = g.epi == NR_EPI_ATOMIC || g.epi == NR_EPI_SCATTER;
-#define NR_BIG(A_, B_, TR_) \
-  if (am == A_ && bm == B_ && atomic_epi == !TR_) return launch_big<A_, B_, TR_, NP, BN>(g, splits, s);
-  NR_BIG(KC_GATHER, KC_PLAIN, true)    // gathered projection (fwd)
-  NR_BIG(KC_PLAIN, KC_PLAIN, true)     // y = x Wᵀ
-  NR_BIG(KC_PLAIN, MN_PLAIN, true)     // dgrad (store / scatter-store epilogues)
-  NR_BIG(MN_PLAIN, MN_GATHER, false)   // wgrad over gathered rows
-  NR_BIG(MN_PLAIN, MN_PLAIN, false)    // wgrad
-#undef NR_BIG
-  return -1;
+int launch_big_modes(const Args& g, const GemmRoute& r, hipStream_t s) {
+#define NR_KERN(A_, B_, TR_) gemm_big_kernel<A_, B_, TR_, NP, BN>
+#define NR_ROW(A_, B_, TR_) NR_LAUNCH_ROW(512, BIG_BM, BN, A_, B_, TR_)
+  NR_MODES_BIG(NR_ROW)
+#undef NR_ROW
+#undef NR_KERN
+  return NR_EINVAL(7);
 }
-
-int launch_big_1_256(const Args& g, int am, int bm, int splits, hipStream_t s);   // gemm_big_*.hip
-int launch_big_3_256(const Args& g, int am, int bm, int splits, hipStream_t s);
-int launch_big_1_128(const Args& g, int am, int bm, int splits, hipStream_t s);
-int launch_big_3_128(const Args& g, int am, int bm, int splits, hipStream_t s);
 
 }  // namespace nrfast

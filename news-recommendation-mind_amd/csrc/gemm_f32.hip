@@ -294,106 +294,86 @@ int launch_kc(const Args& g, int ak, int bk, int splits, hipStream_t s) {
   return launch<BM, BN, false, false>(g, splits, s);
 }
 
-int pick_tile(int64_t n) {  // 64 or 128: least padding, ties -> 128
-  const int64_t p64 = (n + 63) / 64 * 64, p128 = (n + 127) / 128 * 128;
-  return p128 <= p64 ? 128 : 64;
+// the generic kernel: any alignment, the scatter-store epilogues as the same sums via atomics
+int launch_generic(const GemmCall& c, const nrfast::GemmRoute& r) {
+  const nrfast::GemmProblem& p = c.p;
+  Args g;
+  g.M = p.M; g.N = p.N; g.K = p.K;
+  g.A = to_op(p.A); g.B = to_op(p.B); g.Cm = to_op(p.c_rows);
+  g.C = c.C; g.ldc = c.ldc; g.bias = c.bias; g.epi = r.epi; g.pad_row = c.pad_row;
+  g.kchunk = r.kchunk;
+  const int ak = p.A->layout == NR_KCONTIG, bk = p.B->layout == NR_KCONTIG;
+  if (r.bm == 128 && r.bn == 128) return launch_kc<128, 128>(g, ak, bk, r.splits, c.stream);
+  if (r.bm == 128 && r.bn == 64) return launch_kc<128, 64>(g, ak, bk, r.splits, c.stream);
+  if (r.bm == 64 && r.bn == 128) return launch_kc<64, 128>(g, ak, bk, r.splits, c.stream);
+  return launch_kc<64, 64>(g, ak, bk, r.splits, c.stream);
 }
 
-}  // namespace
-
-namespace {
-int gemm_static(int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C, int64_t ldc,
-                const float* bias, int32_t epilogue, const nr_operand* c_rows, int64_t pad_row, int32_t split_k,
-                int32_t prec, float* work, int64_t work_elems, float* colsum, int32_t* colsum_folded,
-                hipStream_t stream) {
-  if (M < 0 || N < 0 || K < 0) return NR_EINVAL(0);
-  if (prec != NR_GEMM_F32 && prec != NR_GEMM_BF16X6 && prec != NR_GEMM_BF16) return NR_EINVAL(12);
+// The one entry behind the four exported ones: validates, routes (gemm_route.h), launches.
+// `dyn`: the dynamic form -- device-resident extents and / or a CU cap, fast kernels only; the static
+// form also takes unaligned operands (generic kernel) and small tiles.
+int gemm_entry(bool dyn, int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C,
+               int64_t ldc, const float* bias, int32_t epilogue, const nr_operand* c_rows, int64_t pad_row,
+               int32_t split_k, const int32_t* m_dev, const int32_t* k_dev, int32_t prec, int32_t max_cus, float* work,
+               int64_t work_elems, float* colsum, int32_t* colsum_folded, hipStream_t stream) {
+  if (work_elems < 0 || (work_elems > 0 && !work)) return NR_EINVAL(16);
+  if (colsum_folded) *colsum_folded = 0;
+  if (colsum && !colsum_folded) return NR_EINVAL(17);
+  if (dyn && max_cus < 0) return NR_EINVAL(15);
+  // the device K of the dynamic form must be a multiple of 32, so its bound must be one
+  if (M < 0 || N < 0 || K < 0 || (dyn && K % 32)) return NR_EINVAL(0);
+  // (the two forms have always reported a bad prec under different argument numbers)
+  if (prec != NR_GEMM_F32 && prec != NR_GEMM_BF16X6 && prec != NR_GEMM_BF16) return NR_EINVAL(dyn ? 14 : 12);
   if (epilogue < NR_EPI_STORE || epilogue > NR_EPI_SCATTER_ZEROED) return NR_EINVAL(3);
   if (!A || !B || !C || !A->data || !B->data) return NR_EINVAL(1);
-  if (((A->map != NR_ROWS_PLAIN) && (A->ld & 3)) || ((B->map != NR_ROWS_PLAIN) && (B->ld & 3)))
-    return NR_EINVAL(2);   // gathered tables must be float4-addressable
+  // gathered tables must be float4-addressable; the dynamic form has the fast kernels only, which
+  // need that of every operand
+  if (((dyn || A->map != NR_ROWS_PLAIN) && (A->ld & 3)) || ((dyn || B->map != NR_ROWS_PLAIN) && (B->ld & 3)))
+    return NR_EINVAL(2);
   if (epilogue == NR_EPI_SCATTER && (!c_rows || (c_rows->map != NR_ROWS_PLAIN && !c_rows->rows)))
     return NR_EINVAL(4);
   if ((epilogue == NR_EPI_ACCUM_GATE || epilogue == NR_EPI_STORE_GELU || epilogue == NR_EPI_GELU_GRAD) &&
       (!c_rows || !c_rows->data))
     return NR_EINVAL(4);
+  const bool no_store_rows = (epilogue == NR_EPI_SCATTER_STORE || epilogue == NR_EPI_SCATTER_ZEROED) &&
+                             (!c_rows || c_rows->map != NR_ROWS_GATHER || !c_rows->rows);
+  // the dynamic form checks the scatter-store rows here, the static form only once it has work to
+  // do (after the split_k check and the empty-problem return)
+  if (dyn && no_store_rows) return NR_EINVAL(4);
   if (split_k < 1) split_k = 1;
   if (split_k > 1 && epilogue != NR_EPI_ATOMIC && epilogue != NR_EPI_SCATTER) return NR_EINVAL(5);
-  if (M == 0 || N == 0) return NR_OK;
+  // K == 0: the dynamic form leaves C alone, the static form runs the generic kernel's epilogue on
+  // zero accumulators (C = bias for a store epilogue)
+  if (M == 0 || N == 0 || (dyn && K == 0)) return NR_OK;
+  if (no_store_rows) return NR_EINVAL(4);
 
-  Args g;
-  g.M = M; g.N = N; g.K = K;
-  g.A = to_op(A); g.B = to_op(B); g.Cm = to_op(c_rows);
-  g.C = C; g.ldc = ldc; g.bias = bias; g.epi = epilogue; g.pad_row = pad_row;
-  g.kchunk = (K + split_k - 1) / split_k;
-  g.kchunk = (g.kchunk + 31) / 32 * 32;
-  if (g.kchunk == 0) g.kchunk = 32;
-  const int splits = (int)((K + g.kchunk - 1) / g.kchunk) > 0 ? (int)((K + g.kchunk - 1) / g.kchunk) : 1;
-
-  if ((epilogue == NR_EPI_SCATTER_STORE || epilogue == NR_EPI_SCATTER_ZEROED) &&
-      (!c_rows || c_rows->map != NR_ROWS_GATHER || !c_rows->rows))
-    return NR_EINVAL(4);
-  {
-    const int64_t t128 = ((M + 127) / 128) * ((N + 127) / 128) * splits;
-    // bf16x6 and f32: small problems (< 400 tiles of 128x128) take 64x64 tiles, which only the
-    // exact-f32 kernel has (they are latency-bound, and 128x128 tiles would leave most CUs idle);
-    // larger ones take 128x128 tiles (bf16x6: the split kernels; f32: the exact-f32 128x128 kernel).
-    // bf16: every eligible shape runs on the bf16 kernel (one product per tile is cheap).
-    const int64_t small_min = 400;
-    const int fb = (prec == NR_GEMM_BF16 || t128 >= small_min) ? 128 : 64;
-    const int rc = nr_gemm_fast(M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, fb, fb, nullptr,
-                                nullptr, prec, 0, work, work_elems, colsum, colsum_folded, stream);
-    if (rc != -1) return rc;
-  }
-  // generic kernel: same sums via atomics
-  if (epilogue == NR_EPI_SCATTER_STORE || epilogue == NR_EPI_SCATTER_ZEROED) g.epi = NR_EPI_SCATTER;
-  int bm = pick_tile(M), bn = pick_tile(N);
-  // small problems: prefer 64x64 tiles to fill the 256 CUs
-  if ((int64_t)((M + bm - 1) / bm) * ((N + bn - 1) / bn) * splits < 512) { bm = 64; bn = 64; }
-  // CONV3 operands need a tap-uniform tile: seg must be a multiple of the tile extent
-  // along the axis that carries the taps (k for K-contiguous, m/n otherwise)
-  const int ak = A->layout == NR_KCONTIG;
-  const int bk = B->layout == NR_KCONTIG;
-  if (A->map == NR_ROWS_CONV3 && ak && (A->seg % 32)) return NR_EINVAL(6);
-  if (B->map == NR_ROWS_CONV3 && bk && (B->seg % 32)) return NR_EINVAL(6);
-  if (A->map == NR_ROWS_CONV3 && !ak && (A->seg % bm)) bm = 64;
-  if (B->map == NR_ROWS_CONV3 && !bk && (B->seg % bn)) bn = 64;
-  if ((A->map == NR_ROWS_CONV3 && !ak && (A->seg % bm)) ||
-      (B->map == NR_ROWS_CONV3 && !bk && (B->seg % bn)))
-    return NR_EINVAL(7);
-  if (bm == 128 && bn == 128) return launch_kc<128, 128>(g, ak, bk, splits, stream);
-  if (bm == 128 && bn == 64) return launch_kc<128, 64>(g, ak, bk, splits, stream);
-  if (bm == 64 && bn == 128) return launch_kc<64, 128>(g, ak, bk, splits, stream);
-  return launch_kc<64, 64>(g, ak, bk, splits, stream);
+  GemmCall c{{M, N, K, A, B, c_rows, epilogue, split_k, prec, dyn, m_dev != nullptr, max_cus, work, work_elems,
+              colsum != nullptr},
+             C, ldc, bias, pad_row, m_dev, k_dev, work, colsum, colsum_folded, stream};
+  // the CU count matters to a route only where it sizes a workspace's use
+  const nrfast::GemmRoute r = nrfast::gemm_route(c.p, work ? nr_gemm_device_cus() : 0);
+  if (r.family == nrfast::GEMM_NOT_ELIGIBLE) return NR_EINVAL(r.einval);
+  return r.family == nrfast::GEMM_GENERIC ? launch_generic(c, r) : nr_gemm_fast(c, r);
 }
 
-int gemm_dyn(int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C, int64_t ldc,
-             const float* bias, int32_t epilogue, const nr_operand* c_rows, int64_t pad_row, int32_t split_k,
-             const int32_t* m_dev, const int32_t* k_dev, int32_t prec, int32_t max_cus, float* work,
-             int64_t work_elems, float* colsum, int32_t* colsum_folded, hipStream_t stream);
 }  // namespace
 
 extern "C" int nr_gemm_f32(int64_t M, int64_t N, int64_t K, const nr_operand* A,
                            const nr_operand* B, float* C, int64_t ldc, const float* bias,
                            int32_t epilogue, const nr_operand* c_rows, int64_t pad_row,
                            int32_t split_k, int32_t prec, hipStream_t stream) {
-  return gemm_static(M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, prec, nullptr, 0, nullptr,
-                     nullptr, stream);
+  return gemm_entry(false, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, nullptr, nullptr, prec, 0,
+                    nullptr, 0, nullptr, nullptr, stream);
 }
 
+// m_dev, k_dev NULL and max_cus 0: the static form
 extern "C" int nr_gemm_f32_ws(int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C,
                               int64_t ldc, const float* bias, int32_t epilogue, const nr_operand* c_rows,
                               int64_t pad_row, int32_t split_k, const int32_t* m_dev, const int32_t* k_dev,
                               int32_t prec, int32_t max_cus, float* work, int64_t work_elems, float* colsum,
                               int32_t* colsum_folded, hipStream_t stream) {
-  if (work_elems < 0 || (work_elems > 0 && !work)) return NR_EINVAL(16);
-  if (colsum_folded) *colsum_folded = 0;
-  if (colsum && !colsum_folded) return NR_EINVAL(17);
-  if (!m_dev && !k_dev && max_cus == 0)
-    return gemm_static(M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, prec, work, work_elems,
-                       colsum, colsum_folded, stream);
-  return gemm_dyn(M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec, max_cus, work,
-                  work_elems, colsum, colsum_folded, stream);
+  return gemm_entry(m_dev || k_dev || max_cus != 0, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k,
+                    m_dev, k_dev, prec, max_cus, work, work_elems, colsum, colsum_folded, stream);
 }
 
 // Device-resident extents: M and K are upper bounds (grid sizing); the kernel reads the actual
@@ -403,42 +383,14 @@ extern "C" int nr_gemm_f32_dyn(int64_t M, int64_t N, int64_t K, const nr_operand
                                float* C, int64_t ldc, const float* bias, int32_t epilogue,
                                const nr_operand* c_rows, int64_t pad_row, int32_t split_k, const int32_t* m_dev,
                                const int32_t* k_dev, int32_t prec, hipStream_t stream) {
-  return nr_gemm_f32_dyn_cus(M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec, 0,
-                             stream);
+  return gemm_entry(true, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec, 0,
+                    nullptr, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int nr_gemm_f32_dyn_cus(int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B,
                                    float* C, int64_t ldc, const float* bias, int32_t epilogue,
                                    const nr_operand* c_rows, int64_t pad_row, int32_t split_k, const int32_t* m_dev,
                                    const int32_t* k_dev, int32_t prec, int32_t max_cus, hipStream_t stream) {
-  return gemm_dyn(M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec, max_cus,
-                  nullptr, 0, nullptr, nullptr, stream);
+  return gemm_entry(true, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec,
+                    max_cus, nullptr, 0, nullptr, nullptr, stream);
 }
-
-namespace {
-int gemm_dyn(int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C, int64_t ldc,
-             const float* bias, int32_t epilogue, const nr_operand* c_rows, int64_t pad_row, int32_t split_k,
-             const int32_t* m_dev, const int32_t* k_dev, int32_t prec, int32_t max_cus, float* work,
-             int64_t work_elems, float* colsum, int32_t* colsum_folded, hipStream_t stream) {
-  if (max_cus < 0) return NR_EINVAL(15);
-  if (M < 0 || N < 0 || K < 0 || (K % 32)) return NR_EINVAL(0);
-  if (prec != NR_GEMM_F32 && prec != NR_GEMM_BF16X6 && prec != NR_GEMM_BF16) return NR_EINVAL(14);
-  if (epilogue < NR_EPI_STORE || epilogue > NR_EPI_SCATTER_ZEROED) return NR_EINVAL(3);
-  if (!A || !B || !C || !A->data || !B->data) return NR_EINVAL(1);
-  if ((A->ld & 3) || (B->ld & 3)) return NR_EINVAL(2);
-  if (epilogue == NR_EPI_SCATTER && (!c_rows || (c_rows->map != NR_ROWS_PLAIN && !c_rows->rows)))
-    return NR_EINVAL(4);
-  if ((epilogue == NR_EPI_ACCUM_GATE || epilogue == NR_EPI_STORE_GELU || epilogue == NR_EPI_GELU_GRAD) &&
-      (!c_rows || !c_rows->data))
-    return NR_EINVAL(4);
-  if ((epilogue == NR_EPI_SCATTER_STORE || epilogue == NR_EPI_SCATTER_ZEROED) &&
-      (!c_rows || c_rows->map != NR_ROWS_GATHER || !c_rows->rows))
-    return NR_EINVAL(4);
-  if (split_k < 1) split_k = 1;
-  if (split_k > 1 && epilogue != NR_EPI_ATOMIC && epilogue != NR_EPI_SCATTER) return NR_EINVAL(5);
-  if (M == 0 || N == 0 || K == 0) return NR_OK;
-  const int rc = nr_gemm_fast(M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, 128, 128, m_dev,
-                              k_dev, prec, max_cus, work, work_elems, colsum, colsum_folded, stream);
-  return rc == -1 ? NR_EINVAL(7) : rc;
-}
-}  // namespace

@@ -4,8 +4,8 @@
 
 namespace nrfast {
 
-int launch_modes64(const Args& g, int am, int bm, int splits, hipStream_t s) {
-  return launch_modes<64, 64>(g, am, bm, splits, NR_GEMM_F32, s);
+int launch_modes64(const Args& g, const GemmRoute& r, hipStream_t s) {
+  return launch_modes<64, 64>(g, r, s);
 }
 
 }  // namespace nrfast

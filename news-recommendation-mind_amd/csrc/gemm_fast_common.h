@@ -4,7 +4,7 @@
 #include <stdlib.h>
 
 #include "common.h"
-#include "../../include/newsrec_hip.h"
+#include "gemm_route.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -48,9 +48,6 @@ __device__ __forceinline__ uint2 hi4(float a, float b, float c, float d) {
 }
 constexpr int SROW = 40;          // split LDS image: [plane][row][k] bf16, 32 k + 8 pad (80-B rows)
 constexpr int SPL = 128 * SROW;   // one plane of a 128-row operand tile
-
-// operand modes
-enum { KC_PLAIN = 0, KC_GATHER = 1, KC_CONV3 = 2, MN_PLAIN = 3, MN_GATHER = 4, MN_CONV3 = 5 };
 
 constexpr bool is_kc(int m) { return m <= KC_CONV3; }
 
@@ -575,10 +572,6 @@ __device__ __forceinline__ void epilogue_any(const Args& g, f32x16 (&acc)[TI][TJ
   }
 }
 
-// Floats before the big kernel's tail partial tiles in its NR_EPI_SCATTER_ZEROED workspace (ints
-// {full, rem, pieces, gn} of the launch's stream-K tail, padded to 256 B; gemm_big_impl.h tail_slab_tr)
-constexpr int TAIL_WS_HDR = 64;
-
 // A work unit = one BM x BN output tile x one K split.
 struct Unit {
   int64_t m0, n0, kbeg;
@@ -608,8 +601,10 @@ struct Cursor {
   Unit u;
 };
 
-// Resident-block slots for a kernel instantiation (CUs x occupancy), cached per device.
-template <typename Kern>
+// Resident-block slots (CUs x occupancy) of a persistent kernel of THREADS per workgroup, cached per
+// device.  Every kernel of one width has the same function type, so they share the cache: the first
+// one launched answers for all of them.
+template <int THREADS, typename Kern>
 int resident_slots(Kern k) {
   static int cache[16] = {0};
   int dev = 0;
@@ -617,14 +612,44 @@ int resident_slots(Kern k) {
   if (cache[dev] == 0) {
     int cus = 0, per = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, 256, 0) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, THREADS, 0) != hipSuccess) return 0;
     cache[dev] = cus * per;
   }
   return cache[dev];
 }
 
-// bf16 launches of the 128x128 fast-path operand combinations (gemm_split_*.hip), np = 3 (bf16x6)
-// or 1 (bf16); -1 = not covered
-int launch_split_modes(const Args& g, int am, int bm, int splits, int np, hipStream_t s);
+// Persistent launch of a fast GEMM kernel over its units (BM x BN output tiles x g.splits): one
+// workgroup of THREADS per unit, at most the resident slots of the CUs the call may use.
+template <int THREADS, int BM, int BN, typename Kern>
+int launch_persistent(Kern kern, const Args& g, hipStream_t s) {
+  const int64_t gm = (g.M + BM - 1) / BM, gn = (g.N + BN - 1) / BN;
+  const int64_t units = gm * gn * g.splits;
+  if (units <= 0) return NR_OK;
+  if (units > 0x7fffffff) return NR_EINVAL(0);
+  int grid = (int)units;
+  const int slots = capped_slots(resident_slots<THREADS>(kern), g.max_cus);
+  if (slots > 0 && slots < grid) grid = slots;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(THREADS), 0, s, g);
+  NR_LAUNCH_CHECK();
+  return NR_OK;
+}
+
+// One row of a unit's launch table (the NR_MODES_* lists of gemm_route.h): launches the unit's
+// instantiation NR_KERN(A, B, TR), THREADS wide on BM x BN tiles, when the route `r` names it
+#define NR_LAUNCH_ROW(THREADS_, BM_, BN_, A_, B_, TR_)       \
+  if (r.am == A_ && r.bmode == B_ && r.tr == TR_)            \
+    return launch_persistent<THREADS_, BM_, BN_>(NR_KERN(A_, B_, TR_), g, s);
+
+// the launch tables of the other translation units (each returns NR_EINVAL(7) for a combination it
+// does not instantiate; gemm_route never routes one there)
+int launch_modes64(const Args& g, const GemmRoute& r, hipStream_t s);     // gemm_fast64.hip
+int launch_split_kc1(const Args& g, const GemmRoute& r, hipStream_t s);   // gemm_split_{kc,mn}{1,3}.hip: K- or
+int launch_split_kc3(const Args& g, const GemmRoute& r, hipStream_t s);   // MN-contiguous A, 1 or 3 planes
+int launch_split_mn1(const Args& g, const GemmRoute& r, hipStream_t s);
+int launch_split_mn3(const Args& g, const GemmRoute& r, hipStream_t s);
+int launch_big_1_256(const Args& g, const GemmRoute& r, hipStream_t s);   // gemm_big_<planes>_<BN>.hip
+int launch_big_3_256(const Args& g, const GemmRoute& r, hipStream_t s);
+int launch_big_1_128(const Args& g, const GemmRoute& r, hipStream_t s);
+int launch_big_3_128(const Args& g, const GemmRoute& r, hipStream_t s);
 
 }  // namespace nrfast

@@ -181,44 +181,14 @@ __global__ __launch_bounds__(256, 2) void gemm_fast_kernel(Args g) {
   epilogue_any<TR, TI, TJ>(g, acc, cp.u.m0, cp.u.n0, wm, wn, h, c);
 }
 
-template <int BM, int BN, int AM, int BMODE, bool TR>
-int launch(const Args& g, int splits, hipStream_t s) {
-  const int64_t gm = (g.M + BM - 1) / BM, gn = (g.N + BN - 1) / BN;
-  const int64_t units = gm * gn * splits;
-  if (units <= 0) return NR_OK;
-  if (units > 0x7fffffff) return NR_EINVAL(0);
-  int grid = (int)units;
-  {
-    const int slots = capped_slots(resident_slots(gemm_fast_kernel<BM, BN, AM, BMODE, TR>), g.max_cus);
-    if (slots > 0 && slots < grid) grid = slots;
-  }
-  Args a = g;
-  a.splits = splits;
-  hipLaunchKernelGGL((gemm_fast_kernel<BM, BN, AM, BMODE, TR>), dim3((unsigned)grid), dim3(256), 0, s, a);
-  NR_LAUNCH_CHECK();
-  return NR_OK;
-}
-
 template <int BM, int BN>
-int launch_modes(const Args& g, int am, int bm, int splits, int prec, hipStream_t s) {
-  if (BM == 128 && BN == 128 && prec != NR_GEMM_F32) {
-    const int rc = launch_split_modes(g, am, bm, splits, prec == NR_GEMM_BF16 ? 1 : 3, s);
-    if (rc != -1) return rc;
-  }
-#define NR_AB(A_, B_, TR_) \
-  if (am == A_ && bm == B_ && atomic_epi == !TR_) return launch<BM, BN, A_, B_, TR_>(g, splits, s);
-  // transposed accumulators (float4 stores) for store epilogues, C-major for atomic ones
-  const bool atomic_epi = g.epi == NR_EPI_ATOMIC || g.epi == NR_EPI_SCATTER;
-  NR_AB(KC_GATHER, KC_PLAIN, true)    // fused gather + projection (fwd)
-  NR_AB(KC_CONV3, KC_PLAIN, true)     // conv as K = 3E GEMM (fwd)
-  NR_AB(KC_PLAIN, KC_PLAIN, true)     // plain y = x Wᵀ
-  NR_AB(KC_PLAIN, MN_PLAIN, true)     // dgrad dx = dy W
-  NR_AB(KC_PLAIN, MN_PLAIN, false)    // dgrad scattered into the word-table gradient
-  NR_AB(MN_PLAIN, MN_GATHER, false)   // wgrad dW = dyᵀ table[ids]
-  NR_AB(MN_PLAIN, MN_CONV3, false)    // conv wgrad
-  NR_AB(MN_PLAIN, MN_PLAIN, false)    // wgrad dW = dyᵀ x
-#undef NR_AB
-  return -1;
+int launch_modes(const Args& g, const GemmRoute& r, hipStream_t s) {
+#define NR_KERN(A_, B_, TR_) gemm_fast_kernel<BM, BN, A_, B_, TR_>
+#define NR_ROW(A_, B_, TR_) NR_LAUNCH_ROW(256, BM, BN, A_, B_, TR_)
+  NR_MODES_KC(NR_ROW) NR_MODES_MN(NR_ROW)
+#undef NR_ROW
+#undef NR_KERN
+  return NR_EINVAL(7);
 }
 
 }  // namespace nrfast

@@ -185,54 +185,25 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(Args g) {
   epilogue_any<TR, TI, TJ>(g, acc, cp.u.m0, cp.u.n0, wm, wn, h, c);
 }
 
-template <int AM, int BMODE, bool TR, int NP>
-int launch_split(const Args& g, int splits, hipStream_t s) {
-  const int64_t gm = (g.M + 127) / 128, gn = (g.N + 127) / 128;
-  const int64_t units = gm * gn * splits;
-  if (units <= 0) return NR_OK;
-  if (units > 0x7fffffff) return NR_EINVAL(0);
-  int grid = (int)units;
-  {
-    const int slots = capped_slots(resident_slots(gemm_split_kernel<AM, BMODE, TR, NP>), g.max_cus);
-    if (slots > 0 && slots < grid) grid = slots;
-  }
-  Args a = g;
-  a.splits = splits;
-  hipLaunchKernelGGL((gemm_split_kernel<AM, BMODE, TR, NP>), dim3((unsigned)grid), dim3(256), 0, s, a);
-  NR_LAUNCH_CHECK();
-  return NR_OK;
-}
-
+#define NR_KERN(A_, B_, TR_) gemm_split_kernel<A_, B_, TR_, NP>
+#define NR_ROW(A_, B_, TR_) NR_LAUNCH_ROW(256, 128, 128, A_, B_, TR_)
 // K-contiguous A operand (projections, dgrads)
 template <int NP>
-int launch_split_kc(const Args& g, int am, int bm, int splits, hipStream_t s) {
-  const bool atomic_epi = g.epi == NR_EPI_ATOMIC || g.epi == NR_EPI_SCATTER;
-#define NR_SAB(A_, B_, TR_) \
-  if (am == A_ && bm == B_ && atomic_epi == !TR_) return launch_split<A_, B_, TR_, NP>(g, splits, s);
-  NR_SAB(KC_GATHER, KC_PLAIN, true)
-  NR_SAB(KC_CONV3, KC_PLAIN, true)
-  NR_SAB(KC_PLAIN, KC_PLAIN, true)
-  NR_SAB(KC_PLAIN, MN_PLAIN, true)
-  NR_SAB(KC_PLAIN, MN_PLAIN, false)
-#undef NR_SAB
-  return -1;
+int launch_split_kc(const Args& g, const GemmRoute& r, hipStream_t s) {
+  NR_MODES_KC(NR_ROW)
+  return NR_EINVAL(7);
 }
 
 // MN-contiguous A operand (weight gradients)
 template <int NP>
-int launch_split_mn(const Args& g, int am, int bm, int splits, hipStream_t s) {
-  const bool atomic_epi = g.epi == NR_EPI_ATOMIC || g.epi == NR_EPI_SCATTER;
-  if (!atomic_epi || am != MN_PLAIN) return -1;
-  if (bm == MN_GATHER) return launch_split<MN_PLAIN, MN_GATHER, false, NP>(g, splits, s);
-  if (bm == MN_PLAIN) return launch_split<MN_PLAIN, MN_PLAIN, false, NP>(g, splits, s);
-  if (bm == MN_CONV3 && g.B.seg % 128 == 0) return launch_split<MN_PLAIN, MN_CONV3, false, NP>(g, splits, s);
-  return -1;
+int launch_split_mn(const Args& g, const GemmRoute& r, hipStream_t s) {
+  // the rows of NR_MODES_MN, in the order this unit has always instantiated them
+  NR_ROW(MN_PLAIN, MN_GATHER, false)
+  NR_ROW(MN_PLAIN, MN_PLAIN, false)
+  NR_ROW(MN_PLAIN, MN_CONV3, false)
+  return NR_EINVAL(7);
 }
-
-// one translation unit per (operand family, plane count): gemm_split_{kc,mn}{1,3}.hip
-int launch_split_kc1(const Args& g, int am, int bm, int splits, hipStream_t s);
-int launch_split_kc3(const Args& g, int am, int bm, int splits, hipStream_t s);
-int launch_split_mn1(const Args& g, int am, int bm, int splits, hipStream_t s);
-int launch_split_mn3(const Args& g, int am, int bm, int splits, hipStream_t s);
+#undef NR_ROW
+#undef NR_KERN
 
 }  // namespace nrfast

@@ -3,8 +3,8 @@
 
 namespace nrfast {
 
-int launch_split_kc3(const Args& g, int am, int bm, int splits, hipStream_t s) {
-  return launch_split_kc<3>(g, am, bm, splits, s);
+int launch_split_kc3(const Args& g, const GemmRoute& r, hipStream_t s) {
+  return launch_split_kc<3>(g, r, s);
 }
 
 }  // namespace nrfast

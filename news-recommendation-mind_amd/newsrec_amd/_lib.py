@@ -44,19 +44,18 @@ class nr_adam_tensor(ctypes.Structure):
                 ("row_touched", ctypes.c_void_p), ("row_len", c_i64)]
 
 
+# the GEMM entries share M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k; then come the
+# device extents (m_dev, k_dev), prec, max_cus, the workspace (work, work_elems, colsum, colsum_folded)
+# as far as the entry has them, and the stream
+_GEMM = [c_i64, c_i64, c_i64, ctypes.POINTER(nr_operand), ctypes.POINTER(nr_operand), c_ptr, c_i64, c_ptr, c_i32,
+         ctypes.POINTER(nr_operand), c_i64, c_i32]
+
 # name -> argtypes (restype int32 unless listed in _RESTYPES)
 _SIGS = {
-    "nr_gemm_f32": [c_i64, c_i64, c_i64, ctypes.POINTER(nr_operand), ctypes.POINTER(nr_operand),
-                    c_ptr, c_i64, c_ptr, c_i32, ctypes.POINTER(nr_operand), c_i64, c_i32, c_i32, c_ptr],
-    "nr_gemm_f32_dyn": [c_i64, c_i64, c_i64, ctypes.POINTER(nr_operand), ctypes.POINTER(nr_operand),
-                        c_ptr, c_i64, c_ptr, c_i32, ctypes.POINTER(nr_operand), c_i64, c_i32, c_ptr, c_ptr, c_i32,
-                        c_ptr],
-    "nr_gemm_f32_dyn_cus": [c_i64, c_i64, c_i64, ctypes.POINTER(nr_operand), ctypes.POINTER(nr_operand),
-                            c_ptr, c_i64, c_ptr, c_i32, ctypes.POINTER(nr_operand), c_i64, c_i32, c_ptr, c_ptr, c_i32,
-                            c_i32, c_ptr],
-    "nr_gemm_f32_ws": [c_i64, c_i64, c_i64, ctypes.POINTER(nr_operand), ctypes.POINTER(nr_operand),
-                       c_ptr, c_i64, c_ptr, c_i32, ctypes.POINTER(nr_operand), c_i64, c_i32, c_ptr, c_ptr, c_i32,
-                       c_i32, c_ptr, c_i64, c_ptr, ctypes.POINTER(c_i32), c_ptr],
+    "nr_gemm_f32": _GEMM + [c_i32, c_ptr],
+    "nr_gemm_f32_dyn": _GEMM + [c_ptr, c_ptr, c_i32, c_ptr],
+    "nr_gemm_f32_dyn_cus": _GEMM + [c_ptr, c_ptr, c_i32, c_i32, c_ptr],
+    "nr_gemm_f32_ws": _GEMM + [c_ptr, c_ptr, c_i32, c_i32, c_ptr, c_i64, c_ptr, ctypes.POINTER(c_i32), c_ptr],
     "nr_gemm_splitk_workspace": [],
     "nr_score_nll_fwd": [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr],
     "nr_score_nll_workspace": [c_i64],

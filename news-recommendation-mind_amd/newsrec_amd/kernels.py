@@ -79,21 +79,18 @@ def gemm(M, N, K, A, B, C, ldc=None, bias=None, epilogue=L.EPI_STORE, c_rows=Non
         raise L.HipError("gemm: bias has %d < N=%d entries" % (bias.numel(), N))
     if colsum is not None and (colsum.numel() < M or not colsum.is_contiguous()):
         raise L.HipError("gemm: colsum must be a contiguous [M] float tensor")
-    if epilogue == L.EPI_ATOMIC and split_k > 1 and colsum is not None:
-        # the workspace path only where it carries the bias gradient: alone (plain partial stores +
-        # one reduction) it measured slower than the atomic epilogue on the NRMS weight gradient
-        # (292-301 vs 277 µs) and equal on the BERT ones; with the column sums folded in it saves
-        # the two colsum launches (BERT FFN: 401 µs vs 409 + colsum)
-        work = _splitk_work(C)
-        folded = ctypes.c_int32(0)
-        L.call("nr_gemm_f32_ws", M, N, K, A, B, L.ptr(C), ldc if ldc is not None else C.stride(0),
-               L.ptr(bias), epilogue, c_rows, pad_row, split_k, None, None, _prec(prec), 0, L.ptr(work),
-               work.numel(), L.ptr(colsum), ctypes.byref(folded) if colsum is not None else None,
-               L.stream_ptr(C))
-        return bool(folded.value)
-    L.call("nr_gemm_f32", M, N, K, A, B, L.ptr(C), ldc if ldc is not None else C.stride(0),
-           L.ptr(bias), epilogue, c_rows, pad_row, split_k, _prec(prec), L.stream_ptr(C))
-    return False
+    # the workspace path only where it carries the bias gradient: alone (plain partial stores +
+    # one reduction) it measured slower than the atomic epilogue on the NRMS weight gradient
+    # (292-301 vs 277 µs) and equal on the BERT ones; with the column sums folded in it saves
+    # the two colsum launches (BERT FFN: 401 µs vs 409 + colsum)
+    ws = epilogue == L.EPI_ATOMIC and split_k > 1 and colsum is not None
+    work = _splitk_work(C) if ws else None
+    folded = ctypes.c_int32(0)
+    L.call("nr_gemm_f32_ws", M, N, K, A, B, L.ptr(C), ldc if ldc is not None else C.stride(0),
+           L.ptr(bias), epilogue, c_rows, pad_row, split_k, None, None, _prec(prec), 0, L.ptr(work),
+           work.numel() if ws else 0, L.ptr(colsum) if ws else None, ctypes.byref(folded) if ws else None,
+           L.stream_ptr(C))
+    return bool(folded.value)
 
 
 def _splitk_work(like):
@@ -119,20 +116,17 @@ def gemm_dyn(M, N, K, A, B, C, m_dev=None, k_dev=None, ldc=None, bias=None, epil
         raise L.HipError("gemm_dyn: bias has %d < N=%d entries" % (bias.numel(), N))
     if K % 32:
         raise L.HipError("gemm_dyn: K must be a multiple of 32")
-    if workspace and ((epilogue == L.EPI_ATOMIC and split_k > 1) or epilogue == L.EPI_SCATTER_ZEROED):
-        work = _splitk_work(C)
-        L.call("nr_gemm_f32_ws", M, N, K, A, B, L.ptr(C), ldc if ldc is not None else C.stride(0),
-               L.ptr(bias), epilogue, c_rows, pad_row, split_k, L.ptr(m_dev), L.ptr(k_dev), _prec(prec),
-               int(max_cus), L.ptr(work), work.numel(), L.ptr(None), None, L.stream_ptr(C))
+    ws = workspace and ((epilogue == L.EPI_ATOMIC and split_k > 1) or epilogue == L.EPI_SCATTER_ZEROED)
+    work = _splitk_work(C) if ws else None
+    if m_dev is None and k_dev is None and not max_cus and not ws:
+        # nr_gemm_f32_ws takes a call with neither device extent nor CU cap for the static form,
+        # which picks other tiles: only nr_gemm_f32_dyn reaches the dynamic form then
+        L.call("nr_gemm_f32_dyn", M, N, K, A, B, L.ptr(C), ldc if ldc is not None else C.stride(0),
+               L.ptr(bias), epilogue, c_rows, pad_row, split_k, None, None, _prec(prec), L.stream_ptr(C))
         return
-    if max_cus:
-        L.call("nr_gemm_f32_dyn_cus", M, N, K, A, B, L.ptr(C), ldc if ldc is not None else C.stride(0),
-               L.ptr(bias), epilogue, c_rows, pad_row, split_k, L.ptr(m_dev), L.ptr(k_dev), _prec(prec),
-               int(max_cus), L.stream_ptr(C))
-        return
-    L.call("nr_gemm_f32_dyn", M, N, K, A, B, L.ptr(C), ldc if ldc is not None else C.stride(0),
+    L.call("nr_gemm_f32_ws", M, N, K, A, B, L.ptr(C), ldc if ldc is not None else C.stride(0),
            L.ptr(bias), epilogue, c_rows, pad_row, split_k, L.ptr(m_dev), L.ptr(k_dev), _prec(prec),
-           L.stream_ptr(C))
+           int(max_cus), L.ptr(work), work.numel() if ws else 0, None, None, L.stream_ptr(C))
 
 
 def _ceil32(n):

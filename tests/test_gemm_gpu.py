@@ -107,3 +107,36 @@ def test_gemm_conv3():
            dwr, epilogue=L.EPI_ATOMIC, split_k=3)
     want_dw = wd.grad.permute(0, 2, 1).reshape(H, 3 * E)
     torch.testing.assert_close(dwr.cpu().double(), want_dw, rtol=0, atol=2e-3)
+
+
+def test_gemm_entries_are_one_entry():
+    """The four exported entries forward to one: nr_gemm_f32 and the static form of nr_gemm_f32_ws give
+    bit-identical C, and so do nr_gemm_f32_dyn, nr_gemm_f32_dyn_cus(max_cus=0) and the dynamic form of
+    nr_gemm_f32_ws (m_dev = 150: rows past it stay untouched).  Deterministic store epilogue with a bias,
+    exact f32; the two forms take different tiles, so only the results within a form are compared."""
+    g = torch.Generator().manual_seed(17)
+    M, N, Kd, m_eff = 200, 136, 96, 150
+    a = torch.randn(M, Kd, generator=g)
+    b = torch.randn(N, Kd, generator=g)
+    bias = torch.randn(N, generator=g)
+    want = (a.double() @ b.double().t() + bias.double()).float()
+    ad, bd, biasd = a.cuda(), b.cuda(), bias.cuda()
+    A, B = K.operand(ad, L.KCONTIG), K.operand(bd, L.KCONTIG)
+    m_dev = torch.tensor([m_eff], dtype=torch.int32, device="cuda")
+
+    def run(name, *tail):
+        C = torch.full((M, N), 7.0, device="cuda")
+        L.call(name, M, N, Kd, A, B, L.ptr(C), N, L.ptr(biasd), L.EPI_STORE, None, -1, 1, *tail, L.stream_ptr(C))
+        torch.cuda.synchronize()
+        return C.cpu()
+
+    static = [run("nr_gemm_f32", L.GEMM_F32),
+              run("nr_gemm_f32_ws", None, None, L.GEMM_F32, 0, None, 0, None, None)]
+    dyn = [run("nr_gemm_f32_dyn", L.ptr(m_dev), None, L.GEMM_F32),
+           run("nr_gemm_f32_dyn_cus", L.ptr(m_dev), None, L.GEMM_F32, 0),
+           run("nr_gemm_f32_ws", L.ptr(m_dev), None, L.GEMM_F32, 0, None, 0, None, None)]
+    assert torch.equal(static[0], static[1])
+    assert torch.equal(dyn[0], dyn[1]) and torch.equal(dyn[0], dyn[2])
+    torch.testing.assert_close(static[0], want, rtol=0, atol=_ref_tol(a, b.t()))
+    torch.testing.assert_close(dyn[0][:m_eff], want[:m_eff], rtol=0, atol=_ref_tol(a, b.t()))
+    assert torch.all(dyn[0][m_eff:] == 7.0)

@@ -9,10 +9,10 @@ OUT=$ROOT/ab/$NAME
 PKG=$ROOT/news-recommendation-mind_amd
 OBJ=$PKG/newsrec_amd/lib/obj
 mkdir -p $OUT && rm -f $OUT/*.o
-git -C $ROOT show $REV:news-recommendation-mind_amd/csrc/$UNIT > $PKG/csrc/.ab_$UNIT
+# the revision's copy lives under $OUT (never in csrc/); -I csrc resolves the unit's relative includes
+git -C $ROOT show $REV:news-recommendation-mind_amd/csrc/$UNIT > $OUT/$UNIT
 extra=$(python3 -c "import sys; sys.path.insert(0, '$PKG'); import build; print(' '.join(build.EXTRA.get('$UNIT', [])))")
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -I$ROOT/include $extra -x hip -c $PKG/csrc/.ab_$UNIT -o $OUT/$UNIT.o
-rm -f $PKG/csrc/.ab_$UNIT
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -I$ROOT/include -I$PKG/csrc $extra -x hip -c $OUT/$UNIT -o $OUT/$UNIT.o
 objs=$(ls $OBJ/*.o | grep -v "/$UNIT\.")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/libnewsrec_hip.so $objs $OUT/$UNIT.o
 echo $OUT/libnewsrec_hip.so
