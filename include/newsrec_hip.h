@@ -629,6 +629,43 @@ int nr_impression_metrics(const float* preds, const int32_t* labels, const int64
                           int64_t G, const int32_t* ks, int32_t nk, double* out, int32_t* flags,
                           hipStream_t stream);
 
+/* ---------------------------------------------------------------- MIND prediction.txt
+ * (csrc/predict.hip).  The tail of Manager.test (utils/Manager.py:842-850): per impression
+ *   rank_list = ss.rankdata(1 - np.asarray(pred), method="ordinal")
+ *   line = str(index) + " [" + ",".join(str(i) for i in rank_list) + "]" + "\n"
+ * over packed scores preds[grp_off[g] .. grp_off[g+1]) of G impressions; `index` = first_line + g.
+ *
+ * pred is a list of Python floats, so the key is the f64 value 1.0 - (double)p, which is NOT
+ * injective on fp32 scores (p < 2^-29 or so collide), and ordinal ranking orders equal keys by
+ * position.  All comparisons are in f64:
+ *   key_i = 1.0 - (double)preds[i]
+ *   rank_i = 1 + #{ j in the group : key_j < key_i or (key_j == key_i and j < i) }
+ * +-inf, +-0.0 and scores outside [0, 1] (NR_SCORE_RAW scores) are ordinary inputs.  A NaN has no
+ * ordinal rank: *status |= NR_RANK_NAN and the caller raises. */
+#define NR_RANK_MAX_GROUP 16384
+enum nr_rank_flags { NR_RANK_NAN = 8, NR_RANK_GROUP_TOO_LARGE = 16 };
+
+/* rank [n] int32 and line_len [G] int64 = the exact byte count of impression g's line.  One wave
+ * per impression; groups of 0 .. NR_RANK_MAX_GROUP candidates.  max_group: the largest group
+ * size, which the caller takes from its host-side offsets (or a device reduction): above
+ * NR_RANK_MAX_GROUP the entry returns NR_EINVAL(2) and launches nothing.  A launch that meets a
+ * larger group all the same (max_group understated) leaves it unranked and sets
+ * NR_RANK_GROUP_TOO_LARGE in *status.  status is OR-ed into; the caller zeroes it. */
+int nr_rank_ordinal(const float* preds, const int64_t* grp_off, int64_t G, int64_t first_line,
+                    int64_t max_group, int32_t* rank, int64_t* line_len, int32_t* status,
+                    hipStream_t stream);
+
+/* The text of Manager.py:847-849: at text + line_off[g], exactly the bytes of
+ *   str(first_line + g) + " [" + ",".join(str(r) for r in rank[grp_off[g] .. grp_off[g+1])) + "]\n"
+ * (ASCII, no padding; an empty group gives "N []\n").  line_off [G+1] int64 = the exclusive prefix
+ * sum of nr_rank_ordinal's line_len, relative to this call's first group; text_bytes = line_off[G],
+ * which the caller knows from sizing the buffer.  text_bytes below 5 G (the shortest line is
+ * "N []\n") returns NR_EINVAL(3); the kernel stores nothing at or past text + text_bytes.  Lines are
+ * assembled in LDS and stored as aligned dwords.  Groups of any size. */
+int nr_format_prediction(const int32_t* rank, const int64_t* grp_off, const int64_t* line_off,
+                         int64_t G, int64_t first_line, uint8_t* text, int64_t text_bytes,
+                         hipStream_t stream);
+
 /* ---------------------------------------------------------------- BERT towers (XFormer / PLM)
  * transformers BertModel as models/XFormer.py:68,94 and models/PLM.py:102,121 call it (token
  * type ids never passed: every token takes token_type_embeddings row 0).  The dense layers are

@@ -131,6 +131,8 @@ _SIGS = {
     "nr_score_ragged": [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr,
                         c_ptr, c_ptr],
     "nr_impression_metrics": [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_ptr, c_ptr, c_ptr],
+    "nr_rank_ordinal": [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr],
+    "nr_format_prediction": [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr],
     "nr_bert_embed_fwd": [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_f32,
                           c_f32, c_u64, c_u64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
     "nr_bert_embed_bwd": [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_f32, c_u64, c_u64,
@@ -157,9 +159,11 @@ _RESTYPES = {"nr_segment_rows_sum_workspace": c_i64, "nr_bert_attn_keep_words": 
              "nr_gemm_splitk_workspace": c_i64, "nr_cnn_keypool_workspace": c_i64,
              "nr_build_hash": ctypes.c_char_p}
 
-# enum nr_batch_flags / nr_metric_flags
+# enum nr_batch_flags / nr_metric_flags / nr_rank_flags, NR_RANK_MAX_GROUP
 BATCH_REVERSE_HISTORY, BATCH_SHUFFLE_POS, BATCH_CURSOR = 1, 2, 4
 METRIC_ONE_CLASS, METRIC_NONBINARY = 1, 2
+RANK_NAN, RANK_GROUP_TOO_LARGE = 8, 16
+RANK_MAX_GROUP = 16384
 
 _lib = None
 

@@ -15,6 +15,10 @@ lists with all_gather_object.  Here:
                       of the predictions to rank 0 (instead of all_gather_object of lists)
   cal_metric          per-impression AUC / MRR / nDCG@k / hit@k in one HIP launch
                       (nr_impression_metrics), then the reference's np.mean + round(4)
+  test                Manager.test (:815-852) minus checkpoint loading: eval_fast on a test split,
+                      then prediction.txt with the per-impression ordinal ranks and the text of
+                      every line formed on the device (nr_rank_ordinal, nr_format_prediction)
+                      and copied to the file in bounded slabs
 
 history_from_table: the reference re-encodes each impression's history titles inside
 predict_fast (TwoTowerBaseModel.py:78-83 calls encode_user).  In eval mode the encoder is
@@ -22,6 +26,8 @@ deterministic and row-independent, so the history representations equal the news
 for the same news ids; reading them from the table is the same result without re-running the
 news tower (test_mind_gpu.py checks the two paths agree).
 """
+import os
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -268,3 +274,118 @@ def evaluate(model, store, metrics=("auc", "mean_mrr", "ndcg@5;10"), batch_impr=
         return None
     return cal_metric_packed(preds, labels, grp_off, list(metrics))
 
+
+
+# ---------------------------------------------------------------- prediction.txt (Manager.py:842-850)
+def _check_ragged(preds, grp_off, what):
+    L.require_gpu(preds, grp_off)
+    if preds.dtype != torch.float32 or preds.dim() != 1 or not preds.is_contiguous():
+        raise L.HipError("%s: preds must be a contiguous 1-D float32 CUDA tensor" % what)
+    if grp_off.dtype != torch.int64 or grp_off.dim() != 1 or not grp_off.is_contiguous() or grp_off.numel() < 1:
+        raise L.HipError("%s: grp_off must be a contiguous 1-D int64 CUDA tensor of G + 1 offsets" % what)
+    if grp_off.device != preds.device:
+        raise L.HipError("%s: preds and grp_off are on different devices" % what)
+
+
+def rank_ordinal(preds, grp_off, first_line=1):
+    """ss.rankdata(1 - np.asarray(pred), method="ordinal") for every impression of a packed score
+    vector (Manager.py:845-846): preds fp32 [n], grp_off int64 [G+1] (device tensors) ->
+    (rank int32 [n], line_len int64 [G]); line_len[g] is the byte count of line first_line + g of
+    prediction.txt.  The key is the f64 value 1.0 - (double)p and equal keys rank by position, as
+    the reference's doubles do.  Raises ValueError when a score is NaN (no ordinal rank), HipError
+    when a group has more than RANK_MAX_GROUP candidates."""
+    _check_ragged(preds, grp_off, "rank_ordinal")
+    n, G = preds.numel(), grp_off.numel() - 1
+    sizes = grp_off[1:] - grp_off[:-1]
+    # the offsets index preds inside the kernel: one host read of (first, last, smallest and largest size)
+    probe = torch.stack([grp_off[0], grp_off[-1], sizes.min() if G else grp_off[0] * 0,
+                         sizes.max() if G else grp_off[0] * 0]).tolist()
+    if probe[0] != 0 or probe[1] != n or probe[2] < 0:
+        raise ValueError("rank_ordinal: grp_off is not a CSR offset array over %d scores" % n)
+    rank = torch.empty(n, dtype=torch.int32, device=preds.device)
+    line_len = torch.empty(G, dtype=torch.int64, device=preds.device)
+    status = torch.zeros(1, dtype=torch.int32, device=preds.device)
+    L.call("nr_rank_ordinal", L.ptr(preds), L.ptr(grp_off), G, int(first_line), int(probe[3]), L.ptr(rank),
+           L.ptr(line_len), L.ptr(status), L.stream_ptr(preds))
+    st = int(status.item())
+    if st & L.RANK_GROUP_TOO_LARGE:
+        raise L.HipError("rank_ordinal: a group exceeds %d candidates" % L.RANK_MAX_GROUP)
+    if st & L.RANK_NAN:
+        raise ValueError("rank_ordinal: a score is NaN, which has no ordinal rank")
+    return rank, line_len
+
+
+def _line_offsets(line_len):
+    """Exclusive prefix sum [G+1] of the line lengths."""
+    off = torch.zeros(line_len.numel() + 1, dtype=torch.int64, device=line_len.device)
+    torch.cumsum(line_len, 0, out=off[1:])
+    return off
+
+
+def _format(rank, grp_off, line_off, first_line, text, text_bytes):
+    G = grp_off.numel() - 1
+    if text.numel() < text_bytes:
+        raise L.HipError("format_predictions: text buffer of %d bytes for %d" % (text.numel(), text_bytes))
+    L.call("nr_format_prediction", L.ptr(rank), L.ptr(grp_off), L.ptr(line_off), G, int(first_line), L.ptr(text),
+           int(text_bytes), L.stream_ptr(rank))
+
+
+def format_predictions(preds, grp_off, first_line=1):
+    """The text of prediction.txt for the impressions of a packed score vector, lines numbered
+    first_line, first_line + 1, ... (Manager.py:842-850) -> uint8 device tensor (ASCII)."""
+    rank, line_len = rank_ordinal(preds, grp_off, first_line)
+    line_off = _line_offsets(line_len)
+    total = int(line_off[-1].item())
+    text = torch.empty(total, dtype=torch.uint8, device=preds.device)
+    _format(rank, grp_off, line_off, first_line, text, total)
+    return text
+
+
+def write_predictions(path, preds, grp_off, slab_bytes=64 << 20):
+    """Write prediction.txt (Manager.py:837-850) for a packed score vector; -> bytes written.
+    The whole vector is ranked first (a NaN raises before the file exists); the text is then formed
+    and copied to pinned host memory in slabs of whole lines of at most slab_bytes (one line when
+    that line alone is longer), so the device and host buffers stay bounded on MINDlarge's
+    ~0.3 GB of text.  Line numbers run 1, 2, ... in group order."""
+    if slab_bytes < 1:
+        raise ValueError("slab_bytes must be positive")
+    rank, line_len = rank_ordinal(preds, grp_off, 1)
+    G = line_len.numel()
+    line_off = _line_offsets(line_len)
+    off = line_off.cpu().numpy()
+    slabs, g0 = [], 0
+    while g0 < G:
+        g1 = int(np.searchsorted(off, off[g0] + slab_bytes, side="right")) - 1
+        g1 = min(max(g1, g0 + 1), G)
+        slabs.append((g0, g1))
+        g0 = g1
+    cap = max([int(off[b] - off[a]) for a, b in slabs] + [1])
+    text = torch.empty(cap, dtype=torch.uint8, device=preds.device)
+    host = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
+    parent = os.path.dirname(path)
+    if parent:
+        os.makedirs(parent, exist_ok=True)
+    written = 0
+    with open(path, "wb") as f:
+        for a, b in slabs:
+            nb = int(off[b] - off[a])
+            _format(rank, grp_off[a:b + 1], line_off[a:b + 1] - line_off[a], 1 + a, text, nb)
+            host[:nb].copy_(text[:nb], non_blocking=True)
+            torch.cuda.current_stream(preds.device).synchronize()
+            f.write(memoryview(host.numpy())[:nb])
+            written += nb
+    return written
+
+
+def test(model, store, path, batch_impr=1024, group=None, history_from_table=True):
+    """Manager.test (:815-852) with fast=True, minus the checkpoint load: scores the split with
+    eval_fast and writes prediction.txt to ``path`` on rank 0 (one line per impression, numbered
+    1, 2, ... in order, not by impr_index).  -> path on rank 0, None elsewhere.  Takes test and
+    dev stores (a train split has no impressions to rank)."""
+    if store.mode not in ("test", "dev"):
+        raise ValueError("test needs a test or dev split, not %s" % store.mode)
+    preds, _, grp_off = eval_fast(model, store, batch_impr, group, history_from_table)
+    if preds is None:
+        return None
+    write_predictions(path, preds, grp_off)
+    return path
