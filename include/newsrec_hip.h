@@ -666,6 +666,36 @@ int nr_format_prediction(const int32_t* rank, const int64_t* grp_off, const int6
                          int64_t G, int64_t first_line, uint8_t* text, int64_t text_bytes,
                          hipStream_t stream);
 
+/* ---------------------------------------------------------------- full-corpus top-K retrieval
+ * (csrc/topk.hip).  Dense recall (`--mode recall -rt d`, utils/Manager.py:45,52,117-119, which the
+ * reference leaves to an external index): for each of U users the K best of the N table rows, exact.
+ *   s[i][j] = (the fp32 fmaf chain over k = 0 .. H-1, ascending, from 0.f, of user[i][k] * table[j][k])
+ *             * (1.0f / sqrtf((float)H))           -- nr_score_ragged's scale, raw logits (no sigmoid)
+ * computed on the f32 MFMA with the k-tiles in order, so the value does not depend on the launch
+ * geometry.  Order within a user: score descending, equal scores by ascending row id; slot r of
+ * top_ids / top_scores [U, K] holds the r-th row in that order.  A row is eligible when
+ * row >= first_row, row_mask (uint8 [N], nullable) is nonzero at it, and it is not among the user's E
+ * exclude ids (exclude int64 [U, E], nullable; entries outside [0, N) are ignored -- padding).  With
+ * fewer than K eligible rows the tail holds id -1 and score -inf.  A non-finite score of an eligible
+ * row ORs NR_TOPK_NONFINITE into *status (caller zeroes); the launch completes all the same.
+ * n_slices: the table is searched in that many contiguous row ranges per 64 users, merged by a second
+ * launch; 0 picks a count that fills the chip, 1 .. 64 force one (the result is the same for all).
+ * workspace: nr_topk_workspace(U, N, K, n_slices) bytes, 8-byte aligned (unused when one slice runs).
+ * N <= 2^31 - 1.  Invalid arguments, nothing launched: 0 a negative size or H < 1, 1 a null required
+ * pointer, 2 K outside [1, NR_TOPK_MAX_K], 3 E above NR_TOPK_MAX_EXCLUDE, 4 ldt or ldu below H,
+ * 5 n_slices above 64, 6 workspace missing or too small, 7 the kernel's launch bound or LDS limit is
+ * below what the launch needs.  U == 0 returns 0 and launches nothing. */
+#define NR_TOPK_MAX_K 128
+#define NR_TOPK_MAX_EXCLUDE 256
+enum nr_topk_flags { NR_TOPK_NONFINITE = 1 };
+/* bytes of workspace that serve the call with these arguments; 0 on bad arguments */
+int64_t nr_topk_workspace(int64_t U, int64_t N, int32_t K, int32_t n_slices);
+int nr_topk_news(const float* table, int64_t ldt, int64_t N, const float* user, int64_t ldu, int64_t U,
+                 int32_t H, int32_t K, int64_t first_row, const uint8_t* row_mask,
+                 const int64_t* exclude, int32_t E, int32_t n_slices, int64_t* top_ids,
+                 float* top_scores, void* workspace, int64_t workspace_bytes, int32_t* status,
+                 hipStream_t stream);
+
 /* ---------------------------------------------------------------- BERT towers (XFormer / PLM)
  * transformers BertModel as models/XFormer.py:68,94 and models/PLM.py:102,121 call it (token
  * type ids never passed: every token takes token_type_embeddings row 0).  The dense layers are

@@ -133,6 +133,9 @@ _SIGS = {
     "nr_impression_metrics": [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_ptr, c_ptr, c_ptr],
     "nr_rank_ordinal": [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr],
     "nr_format_prediction": [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr],
+    "nr_topk_workspace": [c_i64, c_i64, c_i32, c_i32],
+    "nr_topk_news": [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i32, c_i32, c_i64, c_ptr, c_ptr, c_i32, c_i32, c_ptr,
+                     c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "nr_bert_embed_fwd": [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_f32,
                           c_f32, c_u64, c_u64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
     "nr_bert_embed_bwd": [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_f32, c_u64, c_u64,
@@ -157,13 +160,17 @@ _SIGS = {
 _RESTYPES = {"nr_segment_rows_sum_workspace": c_i64, "nr_bert_attn_keep_words": c_i64, "nr_unique_rows_workspace": c_i64, "nr_bert_attn_bwd_workspace": c_i64,
              "nr_colsum_workspace": c_i64, "nr_score_nll_workspace": c_i64,
              "nr_gemm_splitk_workspace": c_i64, "nr_cnn_keypool_workspace": c_i64,
-             "nr_build_hash": ctypes.c_char_p}
+             "nr_topk_workspace": c_i64, "nr_build_hash": ctypes.c_char_p}
 
 # enum nr_batch_flags / nr_metric_flags / nr_rank_flags, NR_RANK_MAX_GROUP
 BATCH_REVERSE_HISTORY, BATCH_SHUFFLE_POS, BATCH_CURSOR = 1, 2, 4
 METRIC_ONE_CLASS, METRIC_NONBINARY = 1, 2
 RANK_NAN, RANK_GROUP_TOO_LARGE = 8, 16
 RANK_MAX_GROUP = 16384
+# enum nr_topk_flags, NR_TOPK_MAX_K, NR_TOPK_MAX_EXCLUDE
+TOPK_NONFINITE = 1
+TOPK_MAX_K = 128
+TOPK_MAX_EXCLUDE = 256
 
 _lib = None
 

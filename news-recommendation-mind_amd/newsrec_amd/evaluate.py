@@ -389,3 +389,137 @@ def test(model, store, path, batch_impr=1024, group=None, history_from_table=Tru
         return None
     write_predictions(path, preds, grp_off)
     return path
+
+
+# ---------------------------------------------------------------- full-corpus retrieval (--mode recall -rt d)
+def topk_news(table, user, k, first_row=1, row_mask=None, exclude=None, n_slices=0):
+    """The k best rows of ``table`` [N, H] for every row of ``user`` [U, H], exact (csrc/topk.hip):
+    score = table[j] . user[i] / sqrt(H) as score_ragged's raw logits, ordered by score descending
+    and, among equal scores, row id ascending.  -> (ids int64 [U, k], scores fp32 [U, k]).
+
+    Eligible rows: j >= first_row (1 skips the padded "" news), row_mask[j] != 0 (uint8 [N], optional)
+    and j not in exclude[i] (int64 [U, E], optional; entries outside [0, N) are padding).  With fewer
+    than k eligible rows the tail is id -1 / score -inf.  n_slices: launch geometry (0 = automatic);
+    the result does not depend on it.  Raises ValueError when an eligible row's score is not finite."""
+    L.require_gpu(table, user, row_mask, exclude)
+    for t, name in ((table, "table"), (user, "user")):
+        if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(-1) != 1):
+            raise L.HipError("topk_news: %s must be a row-major 2-D float32 CUDA tensor" % name)
+    N, H = table.shape
+    U = user.shape[0]
+    if user.shape[1] != H:
+        raise L.HipError("topk_news: user width %d != table width %d" % (user.shape[1], H))
+    if user.device != table.device:
+        raise L.HipError("topk_news: table and user are on different devices")
+    k = int(k)
+    if not 1 <= k <= L.TOPK_MAX_K:
+        raise L.HipError("topk_news: k = %d outside [1, %d]" % (k, L.TOPK_MAX_K))
+    if row_mask is not None:
+        if row_mask.dtype != torch.uint8 or row_mask.dim() != 1 or row_mask.numel() != N:
+            raise L.HipError("topk_news: row_mask must be uint8 [%d]" % N)
+        row_mask = row_mask.contiguous()
+    E = 0
+    if exclude is not None:
+        if exclude.dtype != torch.int64 or exclude.dim() != 2 or exclude.shape[0] != U:
+            raise L.HipError("topk_news: exclude must be int64 [%d, E]" % U)
+        E = exclude.shape[1]
+        if E > L.TOPK_MAX_EXCLUDE:
+            raise L.HipError("topk_news: %d exclude ids per user, at most %d" % (E, L.TOPK_MAX_EXCLUDE))
+        exclude = exclude.contiguous() if E else None
+    dev = table.device
+    ids = torch.empty(U, k, dtype=torch.int64, device=dev)
+    scores = torch.empty(U, k, dtype=torch.float32, device=dev)
+    if U == 0:
+        return ids, scores
+    ws_bytes = int(L.load().nr_topk_workspace(U, N, k, int(n_slices)))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.call("nr_topk_news", L.ptr(table), table.stride(0), N, L.ptr(user), user.stride(0), U, H, k, int(first_row),
+           L.ptr(row_mask), L.ptr(exclude), E, int(n_slices), L.ptr(ids), L.ptr(scores), L.ptr(ws), ws_bytes,
+           L.ptr(status), L.stream_ptr(table))
+    if int(status.item()) & L.TOPK_NONFINITE:
+        raise ValueError("topk_news: a non-finite score among the eligible rows")
+    return ids, scores
+
+
+@torch.no_grad()
+def recommend(model, store, k=10, batch_impr=1024, candidates="impressed", exclude_history=True, news_table=None):
+    """Dense recall over a dev or test split: the k best news of the WHOLE table for every impression's
+    user, one row per impression (not per chunk).  -> (ids int64 [n_impr, k], scores fp32 [n_impr, k]),
+    n_impr = len(store.grp_off_host) - 1.
+
+    The store is walked in eval_batch batches of ``batch_impr`` chunks; an impression cut into several
+    chunks shares its history, so its first chunk (store.first_chunk_host) gives its user
+    (user_reprs with history_from_table).  candidates: "impressed" searches the rows that occur in
+    store.cand_ids (the reference's news_set, construct_cddidx_for_recall, Manager.py:1089-1113), "all"
+    every row except the padded row 0.  exclude_history: the impression's own history is not recommended.
+    news_table: an encode_news_table result to reuse.  Single process: the impressions are not sharded
+    over ranks (no ``group`` argument)."""
+    if store.mode not in ("dev", "test"):
+        raise ValueError("recommend needs a dev or test split, not %s" % store.mode)
+    if candidates not in ("impressed", "all"):
+        raise ValueError("candidates must be 'impressed' or 'all'")
+    was_training = model.training
+    model.eval()
+    table = news_table if news_table is not None else encode_news_table(model, store)
+    dev = table.device
+    mask = None
+    if candidates == "impressed":
+        mask = torch.zeros(table.shape[0], dtype=torch.uint8, device=dev)
+        mask[store.cand_ids] = 1
+    first = store.first_chunk_host
+    n_impr = len(first)
+    ids = torch.empty(n_impr, k, dtype=torch.int64, device=dev)
+    scores = torch.empty(n_impr, k, dtype=torch.float32, device=dev)
+    cache = {}
+    for c0 in range(0, len(store), batch_impr):
+        b = min(batch_impr, len(store) - c0)
+        i0, i1 = np.searchsorted(first, [c0, c0 + b])
+        if i0 == i1:
+            continue
+        x = store.eval_batch(c0, b)
+        rows = torch.from_numpy(first[i0:i1] - c0).to(dev)
+        sub = {key: x[key][rows] for key in ("impr_index", "user_id", "his_id", "his_mask")}
+        user = user_reprs(model, table, sub, True, cache)
+        his = sub["his_id"].reshape(i1 - i0, -1) if exclude_history else None
+        ids[i0:i1], scores[i0:i1] = topk_news(table, user, k, first_row=1, row_mask=mask, exclude=his)
+    model.train(was_training)
+    return ids, scores
+
+
+def recall_metrics(top_ids, store, ks=(5, 10)):
+    """hit_score-style retrieval metrics (Manager.py:1240-1255) of ``top_ids`` [n_impr, K] (recommend's
+    ids, best first) against the clicks of a dev split: over the impressions with at least one clicked
+    candidate (store.cand_labels == 1, grouped by store.grp_off),
+      recall@k = |clicked ∩ top-k| / |clicked|,   hit@k = 1 if any clicked candidate is in the top-k,
+    averaged and rounded to 4 places as cal_metric does; "n_impr_scored" counts those impressions.
+    Plain torch on the device the inputs are on (CPU tensors work)."""
+    if store.cand_labels is None:
+        raise ValueError("recall_metrics needs a dev split with labels")
+    dev = top_ids.device
+    grp_off = store.grp_off.to(dev, torch.int64)
+    G = grp_off.numel() - 1
+    if top_ids.dim() != 2 or top_ids.shape[0] != G:
+        raise ValueError("top_ids must be [%d, K], one row per impression" % G)
+    if max(ks) > top_ids.shape[1] or min(ks) < 1:
+        raise ValueError("ks must lie in [1, %d]" % top_ids.shape[1])
+    cand = store.cand_ids.to(dev, torch.int64)
+    sizes = grp_off[1:] - grp_off[:-1]
+    seg = torch.repeat_interleave(torch.arange(G, device=dev), sizes)
+    clicked = store.cand_labels.to(dev) == 1
+    # distinct (impression, clicked news) pairs: a news listed twice counts once
+    span = int(cand.max().item()) + 1 if cand.numel() else 1
+    pairs = torch.unique(seg[clicked] * span + cand[clicked])
+    g, nid = pairs // span, pairs % span
+    n_click = torch.bincount(g, minlength=G)
+    scored = n_click > 0
+    res = {}
+    for k in ks:
+        found = (top_ids[g, :k] == nid[:, None]).any(1)
+        n_hit = torch.bincount(g, weights=found.to(torch.float64), minlength=G)
+        rec = (n_hit[scored] / n_click[scored].to(torch.float64)).cpu().numpy()
+        hit = (n_hit[scored] > 0).to(torch.float64).cpu().numpy()
+        res["recall@{0}".format(k)] = round(float(np.mean(rec)), 4) if rec.size else 0.0
+        res["hit@{0}".format(k)] = round(float(np.mean(hit)), 4) if hit.size else 0.0
+    res["n_impr_scored"] = int(scored.sum().item())
+    return res

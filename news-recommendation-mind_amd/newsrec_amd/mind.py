@@ -203,6 +203,8 @@ class MINDStore:
             grp = np.append(cand_off[first], cand_off[-1]).astype(np.int64)
             self.grp_off_host = grp
             self.grp_off = torch.from_numpy(grp).to(dev)
+            # chunk index of each impression's first chunk (read-only; one user per impression)
+            self.first_chunk_host = first.astype(np.int64)
             self.n_samples = n_chunks
 
     def __len__(self):
