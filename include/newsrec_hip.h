@@ -504,6 +504,58 @@ int nr_adam_multi(const nr_adam_tensor* tensors, int32_t count, float beta1, flo
 int nr_adam_multi_step(const nr_adam_tensor* tensors, int32_t count, float beta1, float beta2, float eps,
                        float weight_decay, float grad_scale, int32_t* ticket, hipStream_t stream);
 
+/* Global-norm gradient clipping and the non-finite step guard (torch.nn.utils.clip_grad_norm_, the
+ * commented-out Manager.py:646; --anomaly, Manager.py:83,710-712), built into the optimizer: a norm
+ * pass leaves a 16-byte clip state on the device, the clipped Adam reads its gradient scale (and,
+ * if asked, a "skip this step" flag) from there.  The gradients are never written, nothing syncs. */
+typedef struct nr_clip_state {   /* 16 bytes of device memory, caller-owned, zero before first use */
+  float   norm;             /* || grad * grad_scale ||_2 over every tensor of the last norm call     */
+  float   scale;            /* what the clipped Adam multiplies each gradient element by             */
+  int32_t nonfinite;        /* 1 when that norm (as a float) is inf or NaN, else 0                   */
+  int32_t nonfinite_total;  /* += nonfinite on every norm call; the library never resets it (sticky) */
+} nr_clip_state;
+
+/* Bytes of `work` nr_grad_norm_multi needs for this list: one double per 4096-element chunk of
+ * every tensor, rounded up to 16 (never 0).  Host arithmetic only; reads `n` (and checks what
+ * nr_grad_norm_multi checks of the list).  Errors: the codes 0-3 of nr_grad_norm_multi. */
+int64_t nr_grad_norm_workspace(const nr_adam_tensor* tensors, int32_t count);
+
+/* The clip state of a gradient list (of each descriptor only grad, n, row_touched and row_len are
+ * read; any count, <= 32 tensors per launch, the result does not depend on how the list is split):
+ *   S = sum over all elements of (double)g * (double)g
+ *   norm      = (float)(|grad_scale| * sqrt(S))
+ *   coef      = max_norm / ((double)norm + 1e-6);  clamped = coef > 1 ? 1 : coef   (a NaN stays NaN)
+ *   scale     = (float)(grad_scale * clamped)
+ *   nonfinite = norm is inf or NaN;  nonfinite_total += nonfinite
+ * so scale is bit-for-bit grad_scale when nothing clips (max_norm = +inf: norm and guard only), an
+ * inf element gives norm = inf and scale = 0, a NaN element gives NaN for both (torch's results).
+ * Deterministic: the 16 bytes are a function of the list and the tensors' contents only -- each
+ * 4096-element chunk has one double partial at a fixed index of `work`, reduced in a fixed shape,
+ * and one finishing workgroup (a launch of its own) walks the partials in ascending index; no
+ * floating-point atomics.  row_touched as in nr_adam_multi: a row flagged 0 holds zeros, adds
+ * nothing, and is not read where a 16-byte load lies wholly inside such rows.
+ * work: 16-B aligned, work_bytes >= nr_grad_norm_workspace(tensors, count); scratch only (it holds
+ * no counter, so there is nothing to keep zero).
+ * Errors (before any HIP call): -1000 count < 0, or tensors NULL with count > 0; -1001 an n < 0 (or
+ * over 2^42); -1002 grad NULL with n > 0; -1003 row_touched with row_len <= 0 or n % row_len != 0;
+ * -1004 state NULL; -1005 work NULL, misaligned or work_bytes too small; -1006 max_norm negative or
+ * NaN; -1007 grad_scale NaN. */
+int nr_grad_norm_multi(const nr_adam_tensor* tensors, int32_t count, float grad_scale, float max_norm,
+                       void* work, int64_t work_bytes, nr_clip_state* state, hipStream_t stream);
+
+/* nr_adam_multi (ticket NULL: host or device step counts as given) or nr_adam_multi_step (ticket
+ * non-NULL: the launch advances the device step counts) with the gradient scale read from
+ * clip->scale on the device: for the same scale bits, bitwise the result of those entries called
+ * with grad_scale = clip->scale.  honor_skip != 0 and clip->nonfinite != 0: the launch stores
+ * nothing -- parameters, both moments and every step_dev stay bit-unchanged -- and still leaves
+ * the ticket zero.
+ * Errors (before any HIP call): -1000 count < 0, or tensors NULL with count > 0; -1001 an n < 0, or
+ * step < 1 without step_dev; -1002 a NULL param / grad / exp_avg / exp_avg_sq with n > 0; -1003 n
+ * over 2^42; -1005 row_touched with row_len <= 0 or n % row_len != 0; -1006 clip NULL. */
+int nr_adam_multi_clip(const nr_adam_tensor* tensors, int32_t count, float beta1, float beta2, float eps,
+                       float weight_decay, const nr_clip_state* clip, int32_t honor_skip,
+                       int32_t* ticket, hipStream_t stream);
+
 /* out[i] = table[idx[i]] rows of E floats (E % 4 == 0).  BERT_Embedding.forward, BERT.py:39. */
 int nr_embedding_fwd(const float* table, int64_t V, int64_t E, const int64_t* idx, int64_t n,
                      float* out, hipStream_t stream);

@@ -302,7 +302,32 @@ __device__ __forceinline__ void adam_st(float* base, int64_t i, float4 v) {
   __builtin_nontemporal_store((adam_f4){v.x, v.y, v.z, v.w}, reinterpret_cast<adam_f4*>(base) + i);
 }
 
-__global__ __launch_bounds__(256) void adam_multi_kernel(AdamMulti a) {
+// kClip (nr_adam_multi_clip): the gradient scale, and with honor_skip the "skip this step" flag, come
+// from the device clip state that nr_grad_norm_multi left (one uniform load per workgroup).  The
+// descriptor of the plain form is unchanged, so its instantiation is the code it was before.
+struct AdamMultiClip : AdamMulti {
+  const nr_clip_state* clip;
+  int32_t honor_skip;
+};
+template <bool kClip> struct AdamArgs { typedef AdamMulti type; };
+template <> struct AdamArgs<true> { typedef AdamMultiClip type; };
+
+template <bool kClip>
+__global__ __launch_bounds__(256) void adam_multi_kernel(typename AdamArgs<kClip>::type a) {
+  // the gradient scale: the clip state's (one uniform load) or, in the plain form, the descriptor's
+  // read where it is used, as before
+  float clip_scale = 0.f;
+#define NR_ADAM_GSCALE (kClip ? clip_scale : a.gscale)
+  if constexpr (kClip) {
+    clip_scale = a.clip->scale;
+    if (a.honor_skip && a.clip->nonfinite) {
+      // a skipped step stores nothing: parameters, moments and step counts stay as they are; the
+      // ticket still goes round so that the launch leaves it zero (workgroup-uniform branch)
+      if (a.ticket && threadIdx.x == 0 && atomicAdd(a.ticket, 1) == (int)gridDim.x - 1)
+        __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+  }
   const int b = blockIdx.x;
   int t = 0;
   while (t + 1 < a.count && b >= a.blk_off[t + 1]) ++t;
@@ -376,10 +401,10 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(AdamMulti a) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int64_t i = base / 4 + u * 256 + threadIdx.x;
-      adam_elem(pp[u].x, gg[u].x, mm[u].x, vv[u].x, a.b1, a.b2, a.eps, a.wd, a.gscale, step, bc2_sqrt);
-      adam_elem(pp[u].y, gg[u].y, mm[u].y, vv[u].y, a.b1, a.b2, a.eps, a.wd, a.gscale, step, bc2_sqrt);
-      adam_elem(pp[u].z, gg[u].z, mm[u].z, vv[u].z, a.b1, a.b2, a.eps, a.wd, a.gscale, step, bc2_sqrt);
-      adam_elem(pp[u].w, gg[u].w, mm[u].w, vv[u].w, a.b1, a.b2, a.eps, a.wd, a.gscale, step, bc2_sqrt);
+      adam_elem(pp[u].x, gg[u].x, mm[u].x, vv[u].x, a.b1, a.b2, a.eps, a.wd, NR_ADAM_GSCALE, step, bc2_sqrt);
+      adam_elem(pp[u].y, gg[u].y, mm[u].y, vv[u].y, a.b1, a.b2, a.eps, a.wd, NR_ADAM_GSCALE, step, bc2_sqrt);
+      adam_elem(pp[u].z, gg[u].z, mm[u].z, vv[u].z, a.b1, a.b2, a.eps, a.wd, NR_ADAM_GSCALE, step, bc2_sqrt);
+      adam_elem(pp[u].w, gg[u].w, mm[u].w, vv[u].w, a.b1, a.b2, a.eps, a.wd, NR_ADAM_GSCALE, step, bc2_sqrt);
       adam_st(e.p, i, pp[u]);
       adam_st(e.m, i, mm[u]);
       adam_st(e.v, i, vv[u]);
@@ -388,7 +413,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(AdamMulti a) {
     for (int64_t i = base + threadIdx.x; i < end; i += 256) {
       float pp = e.p[i], mm = e.m[i], vv = e.v[i];
       const float gv = (!e.rt || e.rt[i / e.rlen]) ? e.g[i] : 0.f;
-      adam_elem(pp, gv, mm, vv, a.b1, a.b2, a.eps, a.wd, a.gscale, step, bc2_sqrt);
+      adam_elem(pp, gv, mm, vv, a.b1, a.b2, a.eps, a.wd, NR_ADAM_GSCALE, step, bc2_sqrt);
       e.p[i] = pp;
       e.m[i] = mm;
       e.v[i] = vv;
@@ -404,6 +429,144 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(AdamMulti a) {
       __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+}
+#undef NR_ADAM_GSCALE
+
+// ---- global gradient norm (nr_grad_norm_multi): sum of squares over every tensor of a list, in
+// double, bit-reproducible.  Pass 1 gives each kAdamChunk-element chunk of the list ONE partial at a
+// fixed index (chunks numbered through the whole list, whatever launch they fall in), reduced inside
+// the workgroup in a fixed shape: a lane's 16 squares in element order, the wave's 64 lanes by a xor
+// butterfly, the four waves in wave order.  Pass 2 is one workgroup that walks the partials in
+// ascending index (fixed lane assignment, fixed tree) and writes the 16-byte clip state.  No
+// floating-point atomics, no dependence on workgroup arrival order.
+struct NormEntry {
+  const float* g;
+  int64_t n;
+  const uint8_t* rt;   // Adam's per-row "gradient non-zero" flags, or null
+  int64_t rlen;
+};
+
+struct NormMulti {
+  NormEntry e[kAdamMulti];
+  int32_t blk_off[kAdamMulti + 1];
+  int count;
+  double* part;   // this launch's first partial (one per workgroup)
+};
+
+// The gradient loads are nontemporal.  Measured both ways on the NRMS parameter set (tools/clip_probe.py,
+// DESIGN.md 4.3d): the norm call alone 19 vs 22 us warm and 27 vs 44 us cold, the graphed clipped
+// step 144-146 vs 149-152 us; plain loads (which would keep the lines in the L2s for the Adam pass
+// that follows) win only the eager step, by 2-3 us.  -DNR_GRAD_NORM_PLAIN_LOADS is that A/B build.
+#ifndef NR_GRAD_NORM_PLAIN_LOADS
+constexpr int kNormAux = 2;   // the buffer load's nt bit
+__device__ __forceinline__ float4 norm_ld(const float* base, int64_t i) {
+  const adam_f4 v = __builtin_nontemporal_load(reinterpret_cast<const adam_f4*>(base) + i);
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+#else
+constexpr int kNormAux = 0;
+__device__ __forceinline__ float4 norm_ld(const float* base, int64_t i) { return adam_ld(base, i); }
+#endif
+
+__device__ __forceinline__ double norm_sq4(double s, float4 g) {
+  s = fma((double)g.x, (double)g.x, s);
+  s = fma((double)g.y, (double)g.y, s);
+  s = fma((double)g.z, (double)g.z, s);
+  return fma((double)g.w, (double)g.w, s);
+}
+
+// every lane of the wave ends with the same sum (xor butterfly: a fixed tree)
+__device__ __forceinline__ double norm_wave_sum(double v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_part_kernel(NormMulti a) {
+  __shared__ double red[4];
+  const int b = blockIdx.x;
+  int t = 0;
+  while (t + 1 < a.count && b >= a.blk_off[t + 1]) ++t;
+  const NormEntry& e = a.e[t];
+  const int64_t base = (int64_t)(b - a.blk_off[t]) * kAdamChunk;
+  const int64_t end = base + kAdamChunk < e.n ? base + kAdamChunk : e.n;
+  double s = 0.0;
+  if ((reinterpret_cast<uintptr_t>(e.g) & 15) == 0 && end - base == kAdamChunk) {
+    // the thread's four 16-B loads in flight together; the row flags as adam_multi_kernel reads them:
+    // a float4 wholly inside rows flagged zero is not read (a buffer load at an out-of-range offset
+    // answers zeros without a memory access), one that reaches into a flagged row is read whole
+    float4 gg[4];
+    if (e.rt && e.n <= (int64_t)0x1fffffff) {
+      bool rd[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t i = base / 4 + u * 256 + threadIdx.x;
+        const int64_t r0 = (4 * i) / e.rlen, r1 = (4 * i + 3) / e.rlen;
+        rd[u] = ((uint32_t)e.rt[r0] | (uint32_t)e.rt[r0 + 1 < r1 ? r0 + 1 : r1] |
+                 (uint32_t)e.rt[r0 + 2 < r1 ? r0 + 2 : r1] | (uint32_t)e.rt[r1]) != 0;
+      }
+      const auto grs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(e.g), 0, (int)(e.n * 4), 0x00020000);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t i = base / 4 + u * 256 + threadIdx.x;
+        const uint32_t off = rd[u] ? (uint32_t)(i * 16) : 0x80000000u;
+        gg[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(grs, (int)off, 0, kNormAux));
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t i = base / 4 + u * 256 + threadIdx.x;
+        bool rd = !e.rt;
+        if (!rd)
+          for (int64_t r = (4 * i) / e.rlen; r <= (4 * i + 3) / e.rlen && !rd; ++r) rd = e.rt[r] != 0;
+        gg[u] = rd ? norm_ld(e.g, i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s = norm_sq4(s, gg[u]);
+  } else {
+    for (int64_t i = base + threadIdx.x; i < end; i += 256) {
+      const float gv = (!e.rt || e.rt[i / e.rlen]) ? e.g[i] : 0.f;
+      s = fma((double)gv, (double)gv, s);
+    }
+  }
+  s = norm_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) a.part[b] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// one workgroup: lane k sums partials k, k + 1024, ... (four running sums, taken in turn), the waves
+// combine through LDS in wave order; thread 0 forms the state in double
+__global__ __launch_bounds__(1024) void grad_norm_final_kernel(const double* __restrict__ part, int64_t nparts,
+                                                               float grad_scale, float max_norm,
+                                                               nr_clip_state* __restrict__ state) {
+  __shared__ double red[16];
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  int64_t i = threadIdx.x;
+  for (; i + 3 * 1024 < nparts; i += 4 * 1024) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] += part[i + u * 1024];
+  }
+#pragma unroll
+  for (int u = 0; u < 3; ++u)   // (at most three are left)
+    if (i + u * 1024 < nparts) acc[u] += part[i + u * 1024];
+  double s = norm_wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double S = 0.0;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) S += red[w];
+  // torch.nn.utils.clip_grad_norm_: coef = max_norm / (norm + 1e-6) clamped to 1 (a NaN stays NaN)
+  const float norm = (float)(fabs((double)grad_scale) * sqrt(S));
+  const double coef = (double)max_norm / ((double)norm + 1e-6);
+  const double clamped = coef > 1.0 ? 1.0 : coef;
+  const int32_t bad = !(fabsf(norm) <= 3.402823466e38f);   // inf or NaN
+  state->norm = norm;
+  state->scale = (float)((double)grad_scale * clamped);
+  state->nonfinite = bad;
+  state->nonfinite_total += bad;
 }
 
 // one wave per output row, float4 along E
@@ -826,20 +989,24 @@ extern "C" int nr_colsum_ws(const float* x, int64_t ldx, int64_t rows, int64_t c
 }
 
 namespace {
-int adam_multi_launch(AdamMulti& a, int64_t blocks, hipStream_t stream) {
+template <bool kClip>
+int adam_multi_launch(typename AdamArgs<kClip>::type& a, int64_t blocks, hipStream_t stream) {
   if (a.count == 0) return NR_OK;
   // only empty tensors (ticket launches): one block with no elements advances their step counts
   if (blocks == 0) blocks = 1;
   a.blk_off[a.count] = (int32_t)blocks;
-  hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(adam_multi_kernel<kClip>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
   NR_LAUNCH_CHECK();
   return NR_OK;
 }
 }  // namespace
 
 namespace {
+// kClip: nr_adam_multi_clip (clip / honor_skip go into the descriptor, grad_scale is unused)
+template <bool kClip>
 int adam_multi_impl(const nr_adam_tensor* tensors, int32_t count, float beta1, float beta2, float eps,
-                    float weight_decay, float grad_scale, int32_t* ticket, hipStream_t stream) {
+                    float weight_decay, float grad_scale, int32_t* ticket, const nr_clip_state* clip,
+                    int32_t honor_skip, hipStream_t stream) {
   if (count < 0 || (count > 0 && !tensors)) return NR_EINVAL(0);
   for (int32_t t = 0; t < count; ++t) {   // validate everything before the first launch
     const nr_adam_tensor& d = tensors[t];
@@ -847,11 +1014,17 @@ int adam_multi_impl(const nr_adam_tensor* tensors, int32_t count, float beta1, f
     if (d.n > 0 && (!d.param || !d.grad || !d.exp_avg || !d.exp_avg_sq)) return NR_EINVAL(2);
     if ((d.n + kAdamChunk - 1) / kAdamChunk > 0x3fffffff) return NR_EINVAL(3);
     if (d.row_touched && d.row_len < 1) return NR_EINVAL(5);
+    if (kClip && d.row_touched && d.n % d.row_len != 0) return NR_EINVAL(5);
   }
-  AdamMulti a;
+  typename AdamArgs<kClip>::type a;
   a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.gscale = grad_scale;
   a.count = 0;
   a.ticket = ticket;
+  if constexpr (kClip) {
+    if (!clip) return NR_EINVAL(6);
+    a.clip = clip;
+    a.honor_skip = honor_skip;
+  }
   int64_t blocks = 0;
   for (int32_t t = 0; t < count; ++t) {
     const nr_adam_tensor& d = tensors[t];
@@ -861,7 +1034,7 @@ int adam_multi_impl(const nr_adam_tensor* tensors, int32_t count, float beta1, f
     if (d.n == 0 && !(ticket && d.step_dev)) continue;
     const int64_t nb = (d.n + kAdamChunk - 1) / kAdamChunk;
     if (a.count == kAdamMulti || blocks + nb > 0x7fffffff) {
-      const int rc = adam_multi_launch(a, blocks, stream);
+      const int rc = adam_multi_launch<kClip>(a, blocks, stream);
       if (rc) return rc;
       a.count = 0;
       blocks = 0;
@@ -878,17 +1051,93 @@ int adam_multi_impl(const nr_adam_tensor* tensors, int32_t count, float beta1, f
     blocks += nb;
     ++a.count;
   }
-  return adam_multi_launch(a, blocks, stream);
+  return adam_multi_launch<kClip>(a, blocks, stream);
+}
+
+// argument checks of nr_grad_norm_workspace / nr_grad_norm_multi -> the list's chunk count, or an error
+int64_t grad_norm_chunks(const nr_adam_tensor* tensors, int32_t count) {
+  if (count < 0 || (count > 0 && !tensors)) return NR_EINVAL(0);
+  int64_t chunks = 0;
+  for (int32_t t = 0; t < count; ++t) {
+    const nr_adam_tensor& d = tensors[t];
+    if (d.n < 0 || (d.n + kAdamChunk - 1) / kAdamChunk > 0x3fffffff) return NR_EINVAL(1);
+    if (d.n > 0 && !d.grad) return NR_EINVAL(2);
+    if (d.row_touched && (d.row_len < 1 || d.n % d.row_len != 0)) return NR_EINVAL(3);
+    chunks += (d.n + kAdamChunk - 1) / kAdamChunk;
+  }
+  return chunks;
 }
 }  // namespace
 
 extern "C" int nr_adam_multi(const nr_adam_tensor* tensors, int32_t count, float beta1, float beta2, float eps,
                              float weight_decay, float grad_scale, hipStream_t stream) {
-  return adam_multi_impl(tensors, count, beta1, beta2, eps, weight_decay, grad_scale, nullptr, stream);
+  return adam_multi_impl<false>(tensors, count, beta1, beta2, eps, weight_decay, grad_scale, nullptr, nullptr, 0,
+                                stream);
 }
 
 extern "C" int nr_adam_multi_step(const nr_adam_tensor* tensors, int32_t count, float beta1, float beta2, float eps,
                                   float weight_decay, float grad_scale, int32_t* ticket, hipStream_t stream) {
   if (!ticket) return NR_EINVAL(4);
-  return adam_multi_impl(tensors, count, beta1, beta2, eps, weight_decay, grad_scale, ticket, stream);
+  return adam_multi_impl<false>(tensors, count, beta1, beta2, eps, weight_decay, grad_scale, ticket, nullptr, 0,
+                                stream);
+}
+
+extern "C" int nr_adam_multi_clip(const nr_adam_tensor* tensors, int32_t count, float beta1, float beta2, float eps,
+                                  float weight_decay, const nr_clip_state* clip, int32_t honor_skip,
+                                  int32_t* ticket, hipStream_t stream) {
+  return adam_multi_impl<true>(tensors, count, beta1, beta2, eps, weight_decay, 1.f, ticket, clip, honor_skip,
+                               stream);
+}
+
+extern "C" int64_t nr_grad_norm_workspace(const nr_adam_tensor* tensors, int32_t count) {
+  const int64_t chunks = grad_norm_chunks(tensors, count);
+  if (chunks < 0) return chunks;
+  // one double per chunk, a whole number of 16-B units, never empty
+  return ((chunks > 0 ? chunks : 1) * (int64_t)sizeof(double) + 15) / 16 * 16;
+}
+
+extern "C" int nr_grad_norm_multi(const nr_adam_tensor* tensors, int32_t count, float grad_scale, float max_norm,
+                                  void* work, int64_t work_bytes, nr_clip_state* state, hipStream_t stream) {
+  const int64_t chunks = grad_norm_chunks(tensors, count);
+  if (chunks < 0) return (int)chunks;
+  if (!state) return NR_EINVAL(4);
+  if (!work || (reinterpret_cast<uintptr_t>(work) & 15) || work_bytes < nr_grad_norm_workspace(tensors, count))
+    return NR_EINVAL(5);
+  if (!(max_norm >= 0.f)) return NR_EINVAL(6);   // negative or NaN
+  if (grad_scale != grad_scale) return NR_EINVAL(7);
+  double* part = static_cast<double*>(work);
+  NormMulti a;
+  a.count = 0;
+  int64_t blocks = 0, done = 0;   // done: chunks of the launches before this one
+  auto launch = [&]() -> int {
+    if (a.count == 0) return NR_OK;
+    a.blk_off[a.count] = (int32_t)blocks;
+    a.part = part + done;
+    hipLaunchKernelGGL(grad_norm_part_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    NR_LAUNCH_CHECK();
+    done += blocks;
+    a.count = 0;
+    blocks = 0;
+    return NR_OK;
+  };
+  for (int32_t t = 0; t < count; ++t) {
+    const nr_adam_tensor& d = tensors[t];
+    if (d.n == 0) continue;
+    const int64_t nb = (d.n + kAdamChunk - 1) / kAdamChunk;
+    if (a.count == kAdamMulti || blocks + nb > 0x7fffffff) {
+      const int rc = launch();
+      if (rc) return rc;
+    }
+    NormEntry& e = a.e[a.count];
+    e.g = d.grad; e.n = d.n; e.rt = d.row_touched; e.rlen = d.row_touched ? d.row_len : 1;
+    a.blk_off[a.count] = (int32_t)blocks;
+    blocks += nb;
+    ++a.count;
+  }
+  const int rc = launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(1024), 0, stream, part, chunks, grad_scale, max_norm,
+                     state);
+  NR_LAUNCH_CHECK();
+  return NR_OK;
 }

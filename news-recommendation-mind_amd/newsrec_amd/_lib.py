@@ -154,13 +154,17 @@ _SIGS = {
     "nr_adam_multi": [ctypes.POINTER(nr_adam_tensor), c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
     "nr_adam_multi_step": [ctypes.POINTER(nr_adam_tensor), c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr,
                            c_ptr],
+    "nr_grad_norm_workspace": [ctypes.POINTER(nr_adam_tensor), c_i32],
+    "nr_grad_norm_multi": [ctypes.POINTER(nr_adam_tensor), c_i32, c_f32, c_f32, c_ptr, c_i64, c_ptr, c_ptr],
+    "nr_adam_multi_clip": [ctypes.POINTER(nr_adam_tensor), c_i32, c_f32, c_f32, c_f32, c_f32, c_ptr, c_i32, c_ptr,
+                           c_ptr],
     "nr_build_hash": [],
 }
 
 _RESTYPES = {"nr_segment_rows_sum_workspace": c_i64, "nr_bert_attn_keep_words": c_i64, "nr_unique_rows_workspace": c_i64, "nr_bert_attn_bwd_workspace": c_i64,
              "nr_colsum_workspace": c_i64, "nr_score_nll_workspace": c_i64,
              "nr_gemm_splitk_workspace": c_i64, "nr_cnn_keypool_workspace": c_i64,
-             "nr_topk_workspace": c_i64, "nr_build_hash": ctypes.c_char_p}
+             "nr_topk_workspace": c_i64, "nr_grad_norm_workspace": c_i64, "nr_build_hash": ctypes.c_char_p}
 
 # enum nr_batch_flags / nr_metric_flags / nr_rank_flags, NR_RANK_MAX_GROUP
 BATCH_REVERSE_HISTORY, BATCH_SHUFFLE_POS, BATCH_CURSOR = 1, 2, 4

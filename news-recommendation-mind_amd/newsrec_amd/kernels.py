@@ -736,13 +736,8 @@ def adam(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, 
            weight_decay, step, L.ptr(step_dev), grad_scale, L.stream_ptr(param))
 
 
-def adam_multi(entries, beta1, beta2, eps, weight_decay, grad_scale=1.0, advance_steps=False):
-    """entries: [(param, grad, exp_avg, exp_avg_sq, lr, step)] with ``step`` an int or an int64 CUDA
-    scalar and ``lr`` a float or a float32 CUDA scalar (read on the device); one nr_adam_multi call
-    (a launch per <= 32 tensors).  ``advance_steps``: the device step counts hold the count BEFORE
-    this step and the launch itself adds 1 to each (nr_adam_multi_step)."""
-    if not entries:
-        return
+def _adam_descriptors(entries, who="adam_multi"):
+    """The nr_adam_tensor array of ``entries`` (adam_multi's tuples), checked."""
     arr = (L.nr_adam_tensor * len(entries))()
     for i, ent in enumerate(entries):
         p, g, m, v, lr, step = ent[:6]
@@ -751,23 +746,34 @@ def adam_multi(entries, beta1, beta2, eps, weight_decay, grad_scale=1.0, advance
         rlen = 0
         if rt is not None:
             if rt.dtype != torch.uint8 or not rt.is_cuda or rt.numel() < 1 or p.numel() % rt.numel():
-                raise L.HipError("adam_multi: row flags must be a uint8 CUDA tensor dividing the parameter")
+                raise L.HipError(who + ": row flags must be a uint8 CUDA tensor dividing the parameter")
             rlen = p.numel() // rt.numel()
         n = p.numel()
         for t in (p, g, m, v):
             if not t.is_contiguous() or t.numel() != n:
-                raise L.HipError("adam_multi: tensors must be contiguous with equal numel")
+                raise L.HipError(who + ": tensors must be contiguous with equal numel")
         sd, ld = 0, 0
         if torch.is_tensor(step):
             if step.dtype != torch.int64 or not step.is_cuda:
-                raise L.HipError("adam_multi: a device step count must be an int64 CUDA tensor")
+                raise L.HipError(who + ": a device step count must be an int64 CUDA tensor")
             sd, step = step.data_ptr(), 0
         if torch.is_tensor(lr):
             if lr.dtype != torch.float32 or not lr.is_cuda or lr.numel() != 1:
-                raise L.HipError("adam_multi: a device learning rate must be a float32 CUDA scalar")
+                raise L.HipError(who + ": a device learning rate must be a float32 CUDA scalar")
             ld, lr = lr.data_ptr(), 0.0
         arr[i] = L.nr_adam_tensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, float(lr), int(step), sd,
                                   ld, rt.data_ptr() if rt is not None else 0, rlen)
+    return arr
+
+
+def adam_multi(entries, beta1, beta2, eps, weight_decay, grad_scale=1.0, advance_steps=False):
+    """entries: [(param, grad, exp_avg, exp_avg_sq, lr, step)] with ``step`` an int or an int64 CUDA
+    scalar and ``lr`` a float or a float32 CUDA scalar (read on the device); one nr_adam_multi call
+    (a launch per <= 32 tensors).  ``advance_steps``: the device step counts hold the count BEFORE
+    this step and the launch itself adds 1 to each (nr_adam_multi_step)."""
+    if not entries:
+        return
+    arr = _adam_descriptors(entries)
     if advance_steps:
         ticket = self_cleaning_workspace(entries[0][0].device, "nr_adam_multi_step", 4)
         L.call("nr_adam_multi_step", arr, len(entries), beta1, beta2, eps, weight_decay, grad_scale,
@@ -775,6 +781,48 @@ def adam_multi(entries, beta1, beta2, eps, weight_decay, grad_scale=1.0, advance
         return
     L.call("nr_adam_multi", arr, len(entries), beta1, beta2, eps, weight_decay, grad_scale,
            L.stream_ptr(entries[0][0]))
+
+
+def _clip_state(state, who):
+    if (not torch.is_tensor(state) or not state.is_cuda or not state.is_contiguous() or
+            state.numel() * state.element_size() != 16 or state.data_ptr() % 4):
+        raise L.HipError(who + ": the clip state must be 16 contiguous bytes of CUDA memory (nr_clip_state)")
+
+
+def clip_state(dev):
+    """A zeroed nr_clip_state on ``dev``: four int32 words (norm and scale are float32 bit patterns)."""
+    return torch.zeros(4, dtype=torch.int32, device=dev)
+
+
+def grad_norm_multi(entries, grad_scale, max_norm, state):
+    """The global gradient norm of ``entries`` (adam_multi's tuples; only the gradients and row flags
+    are read) and the clip factor for ``max_norm`` into ``state`` (nr_clip_state: norm, scale,
+    nonfinite, nonfinite_total), bit-reproducibly and without a host sync (nr_grad_norm_multi).
+    ``max_norm=float("inf")``: norm and non-finite guard only (scale == grad_scale)."""
+    _clip_state(state, "grad_norm_multi")
+    arr = _adam_descriptors(entries, "grad_norm_multi")
+    need = L.load().nr_grad_norm_workspace(arr, len(entries))
+    if need < 0:
+        L.check(int(need), "nr_grad_norm_workspace")
+    # scratch only (the finishing reduction is a launch of its own: no ticket word to keep zero)
+    work = self_cleaning_workspace(state.device, "nr_grad_norm_multi", (need + 3) // 4, clean=[])
+    L.call("nr_grad_norm_multi", arr, len(entries), float(grad_scale), float(max_norm), L.ptr(work),
+           work.numel() * 4, L.ptr(state), L.stream_ptr(state))
+
+
+def adam_multi_clip(entries, beta1, beta2, eps, weight_decay, state, honor_skip=False, advance_steps=False):
+    """adam_multi with the gradient scale read on the device from ``state`` (what grad_norm_multi
+    left there); ``honor_skip``: a state flagged non-finite turns the call into a no-op (nothing is
+    stored, device step counts stand still).  nr_adam_multi_clip."""
+    if not entries:
+        return
+    _clip_state(state, "adam_multi_clip")
+    arr = _adam_descriptors(entries, "adam_multi_clip")
+    ticket = None
+    if advance_steps:
+        ticket = self_cleaning_workspace(entries[0][0].device, "nr_adam_multi_step", 4)
+    L.call("nr_adam_multi_clip", arr, len(entries), beta1, beta2, eps, weight_decay, L.ptr(state),
+           1 if honor_skip else 0, L.ptr(ticket), L.stream_ptr(entries[0][0]))
 
 
 def embedding_fwd(table, idx, out):

@@ -53,15 +53,18 @@ def build_model(encN, encU, hidden, vocab=30522, device="cuda", user_num=40, dro
     return model
 
 
-def get_optim(model, lr=1e-4, bert_lr=6e-6, capturable=False):
+def get_optim(model, lr=1e-4, bert_lr=6e-6, capturable=False, max_grad_norm=None, skip_nonfinite=False):
     """Manager._get_optim: names containing 'bert' -> bert_lr, the rest -> lr.  ``capturable``:
-    step counts on the device (the step can be captured in a graph)."""
+    step counts on the device (the step can be captured in a graph).  ``max_grad_norm``: clip the
+    global gradient norm inside the optimizer (Manager.py:646's commented-out clip_grad_norm_, without
+    rewriting the gradients); ``skip_nonfinite``: drop a step whose norm is inf / NaN (optim.FusedAdam)."""
     from .optim import FusedAdam
     import re
     base, bert = [], []
     for name, p in model.named_parameters():
         (bert if re.search("bert", name) else base).append(p)
-    return FusedAdam([{"params": base, "lr": lr}, {"params": bert, "lr": bert_lr}], capturable=capturable)
+    return FusedAdam([{"params": base, "lr": lr}, {"params": bert, "lr": bert_lr}], capturable=capturable,
+                     max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
 
 
 def train_step(model, optimizer, x, grad_sync=None, check_labels=True):

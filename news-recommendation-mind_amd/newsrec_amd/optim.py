@@ -10,12 +10,34 @@ from . import kernels as K
 class FusedAdam(torch.optim.Optimizer):
     """``capturable=True`` keeps each parameter's step count on the device (one multi-tensor
     add per step, bias corrections formed in the kernel), so ``step()`` can be captured in a
-    graph and replayed — torch.optim.Adam(capturable=True) semantics."""
+    graph and replayed — torch.optim.Adam(capturable=True) semantics.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
+    ``max_grad_norm``: clip the global gradient norm (over every parameter of the step, both param
+    groups, after ``grad_scale``) as ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` would
+    before the step (the reference's commented-out utils/Manager.py:646) -- but inside the
+    optimizer: one deterministic norm pass (nr_grad_norm_multi) leaves the clip factor on the device
+    and the Adam kernel multiplies each gradient by it as it reads it.  ``step()`` NEVER WRITES A
+    GRADIENT: unlike torch's in-place clip, ``.grad`` holds the unclipped values afterwards (and the
+    row-sparse table flags, which an in-place rewrite would invalidate, stay valid).  No host sync;
+    graph-capturable.
+
+    ``skip_nonfinite``: a step whose norm is inf or NaN is dropped -- parameters, moments and step
+    counts keep their values -- instead of poisoning them (``max_grad_norm=None`` then means "norm
+    and guard only").  Capturable mode decides on the device; otherwise ``step()`` reads the flag
+    (ONE host sync per step) before it advances the host step counts.
+
+    ``grad_norm`` (a 0-dim device tensor, no sync) and ``clip_stats()`` (syncs) report the last step."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
+                 max_grad_norm=None, skip_nonfinite=False):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self.capturable = capturable
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError("max_grad_norm must be None or a non-negative number")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clip = None   # the device nr_clip_state (4 words), created by the first clipped step
         # capturable: each group's lr lives on the device too (read by the kernel), so a graph
         # replay follows group["lr"] changes (a warmup scheduler, Manager.py:415-420) once
         # sync_lr() has copied them over -- step() does it when not capturing, GraphedStep before
@@ -36,6 +58,30 @@ class FusedAdam(torch.optim.Optimizer):
                 t.fill_(float(group["lr"]))
                 self._lr_host[i] = group["lr"]
 
+    @property
+    def clipping(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _clip_state(self, dev=None):
+        if self._clip is None:
+            if dev is None:
+                dev = next(p.device for g in self.param_groups for p in g["params"])
+            self._clip = K.clip_state(dev)
+        return self._clip
+
+    @property
+    def grad_norm(self):
+        """The last step's global gradient norm (after ``grad_scale``, before clipping): a 0-dim
+        float32 device tensor viewing the clip state -- log it without a sync."""
+        return self._clip_state().view(torch.float32)[0]
+
+    def clip_stats(self):
+        """{"norm", "scale", "nonfinite", "nonfinite_total"} of the clip state as Python numbers
+        (synchronises).  nonfinite_total counts the non-finite steps since the optimizer was made."""
+        st = self._clip_state()
+        f, i = st.view(torch.float32).tolist(), st.tolist()
+        return {"norm": f[0], "scale": f[1], "nonfinite": i[2], "nonfinite_total": i[3]}
+
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
         """``grad_scale`` multiplies every gradient as it is read (the data-parallel 1/world
@@ -55,6 +101,10 @@ class FusedAdam(torch.optim.Optimizer):
                 # a table sharded across ranks (dist.GradSync(shard_tables=True)): this rank updates
                 # rows [row0, row0 + rows) only, with moments for those rows
                 shard = getattr(p, "_nr_shard", None)
+                if shard is not None and self.clipping:
+                    # the norm of a table sharded across ranks needs a cross-rank sum
+                    raise NotImplementedError("FusedAdam: max_grad_norm / skip_nonfinite with rank-sharded "
+                                              "tables (_nr_shard) is not supported")
                 if shard is not None and shard[1] == 0:
                     continue
                 if len(st) == 0:
@@ -69,18 +119,16 @@ class FusedAdam(torch.optim.Optimizer):
         # step in a few launches instead of one launch per parameter
         batches = {}
         for gi, group, p, st in todo:
-            if not self.capturable:
-                st["step"] += 1
             g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
             key = (tuple(group["betas"]), group["eps"], group["weight_decay"])
             lr = self._lr_dev[gi] if self.capturable else group["lr"]
             shard = getattr(p, "_nr_shard", None)
             if shard is not None:
                 r0, n = shard
-                batches.setdefault(key, []).append((p.data[r0:r0 + n], g[r0:r0 + n], st["exp_avg"], st["exp_avg_sq"],
-                                                    lr, st["step"]))
+                batches.setdefault(key, []).append([p.data[r0:r0 + n], g[r0:r0 + n], st["exp_avg"], st["exp_avg_sq"],
+                                                    lr, st])
                 continue
-            ent = (p, g, st["exp_avg"], st["exp_avg_sq"], lr, st["step"])
+            ent = [p, g, st["exp_avg"], st["exp_avg_sq"], lr, st]
             # a row-sparse table gradient (functions.LOCAL_ROW_GRAD) carries per-row "touched" flags:
             # the kernel skips reading the rows known to be zero
             # rt = (that buffer, or a weak reference to the .grad tensor they were bound to, flags, its
@@ -93,8 +141,30 @@ class FusedAdam(torch.optim.Optimizer):
                 else:
                     ok = p.grad.data_ptr() == rt[0].data_ptr()
                 if ok and p.grad._version == rt[2]:
-                    ent = ent + (rt[1],)
+                    ent.append(rt[1])
             batches.setdefault(key, []).append(ent)
-        for (betas, eps, wd), entries in batches.items():
-            K.adam_multi(entries, betas[0], betas[1], eps, wd, grad_scale, advance_steps=self.capturable)
+
+        def entries_of(batch):   # with the step counts as they are now
+            return [tuple(e[:5]) + (e[5]["step"],) + tuple(e[6:]) for e in batch]
+
+        if self.clipping and todo:
+            # ONE norm over every entry of the step (all batches, both groups), then the clipped Adam
+            # per batch reading the scale (and the skip flag) from the device state
+            state = self._clip_state(todo[0][2].device)
+            max_norm = float("inf") if self.max_grad_norm is None else self.max_grad_norm
+            K.grad_norm_multi([e for b in batches.values() for e in entries_of(b)], grad_scale, max_norm, state)
+            if self.skip_nonfinite and not self.capturable:
+                # host step counts: the decision has to be made here, before they advance (one sync)
+                if int(state[2].item()) != 0:
+                    return loss
+        if not self.capturable:
+            for _, _, _, st in todo:
+                st["step"] += 1
+        for (betas, eps, wd), batch in batches.items():
+            if self.clipping:
+                K.adam_multi_clip(entries_of(batch), betas[0], betas[1], eps, wd, state,
+                                  honor_skip=self.skip_nonfinite, advance_steps=self.capturable)
+            else:
+                K.adam_multi(entries_of(batch), betas[0], betas[1], eps, wd, grad_scale,
+                             advance_steps=self.capturable)
         return loss
