@@ -539,7 +539,8 @@ def attn_pool_fwd(x, q, mask, nseq, seq_len, out, probs, key=None, gamma=None, b
     _rows_ok(x, nseq * seq_len, D, "x")
     _rows_ok(key, nseq * seq_len, D, "key")
     _rows_ok(out, nseq, D, "out")
-    if probs.numel() < nseq * seq_len or (gamma is not None and stats.numel() < 2 * nseq * seq_len):
+    if probs.numel() < nseq * seq_len or (gamma is not None and stats is not None
+                                          and stats.numel() < 2 * nseq * seq_len):
         raise L.HipError("attn_pool_fwd: probs/stats too small")
     mp, mdt = mask_arg(mask, nseq * seq_len)
     scale = 1.0 / float(D) ** 0.5 if scale is None else scale
