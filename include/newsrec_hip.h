@@ -142,6 +142,40 @@ int nr_gemm_f32_ws(int64_t M, int64_t N, int64_t K, const nr_operand* A, const n
                    int64_t pad_row, int32_t split_k, const int32_t* m_dev, const int32_t* k_dev,
                    int32_t prec, int32_t max_cus, float* work, int64_t work_elems, float* colsum,
                    int32_t* colsum_folded, hipStream_t stream);
+/* One nr_gemm_f32_ws call without its stream: the fields are that entry's arguments, in order. */
+typedef struct nr_gemm_desc {
+  int64_t M, N, K;
+  const nr_operand *A, *B;
+  float* C;
+  int64_t ldc;
+  const float* bias;
+  int32_t epilogue;
+  const nr_operand* c_rows;
+  int64_t pad_row;
+  int32_t split_k;
+  const int32_t *m_dev, *k_dev;
+  int32_t prec, max_cus;
+  float* work;
+  int64_t work_elems;
+  float* colsum;
+  int32_t* colsum_folded;
+} nr_gemm_desc;
+
+/* Two INDEPENDENT problems, with the results of nr_gemm_f32_ws(p1) followed by nr_gemm_f32_ws(p2).
+ * They run as ONE kernel launch -- each on a share of the workgroups, walking its units in the order
+ * it has alone, so every output element is computed by the same arithmetic in the same order as in
+ * its own call -- when both route to the exact-f32 64 x 64 kernel (small problems), one is an input
+ * gradient (plain K-contiguous A, plain MN-contiguous B, a store epilogue) and the other a weight
+ * gradient (both operands plain MN-contiguous, an atomic epilogue), in either order, and neither has
+ * device extents or a CU cap.  Any other two problems launch one after the other.  The MHA user
+ * encoder's backward (dx = dY W beside dW += dYᵀ x, both reading dY) is such a pair: each alone fills
+ * under two thirds of the resident workgroup slots.
+ * Both problems are validated before anything launches.  Returns p1's nr_gemm_f32_ws code for a bad
+ * argument of p1, NR_EINVAL(100 + n) for argument n of p2, NR_EINVAL(200) for a NULL description and
+ * NR_EINVAL(201) when the problems are not independent: an output ([M x N] at C, rows ldc apart)
+ * overlapping the other problem's output, bias, auxiliary matrix or operand (a plain operand's whole
+ * matrix; of a gathered / conv3 operand, whose table height the call does not carry, its first row). */
+int nr_gemm_f32_pair(const nr_gemm_desc* p1, const nr_gemm_desc* p2, hipStream_t stream);
 /* floats of split-K workspace that serve any nr_gemm_f32_ws call on the current device */
 int64_t nr_gemm_splitk_workspace(void);
 
@@ -197,6 +231,18 @@ int nr_unique_rows_zero_absent(const int32_t* work, const int32_t* counts, int64
 int nr_segment_rows_sum_multi(const float* src, int64_t lds, int64_t width, int64_t T, const int32_t* seg_off,
                               const int32_t* seg_tok, const int32_t* seg_of, const int32_t* counts,
                               int64_t rows_max, float* work, float* dst, int64_t ldd, hipStream_t stream);
+
+/* nr_segment_rows_sum_multi(src .. ldd) followed by nr_unique_rows_zero_absent(uwork, counts, V, pad_row,
+ * zdst, zldd, zwidth, flags) -- the same outputs, bit for bit, and the same arguments and return codes
+ * (the segment sum's arguments are checked first) -- in two launches instead of three: the zero fill
+ * depends on the distinct-row workspace only, so its workgroups ride in the segment sum's second
+ * (fix-up) launch, behind the fix-up's own.  No workgroup waits for another.  zdst must not overlap
+ * dst or work. */
+int nr_segment_rows_sum_multi_zero(const float* src, int64_t lds, int64_t width, int64_t T, const int32_t* seg_off,
+                                   const int32_t* seg_tok, const int32_t* seg_of, const int32_t* counts,
+                                   int64_t rows_max, float* work, float* dst, int64_t ldd, const int32_t* uwork,
+                                   int64_t V, int64_t pad_row, float* zdst, int64_t zldd, int64_t zwidth,
+                                   uint8_t* flags, hipStream_t stream);
 
 /* The CNN encoder's k = 3 convolution per distinct row (CNN.py:41, Conv1d(E -> H, k = 3, pad = 1)).
  * nr_segment_rows_sum_conv3: dst[u][tap*tap_width + c] = sum over the CSR tokens t of distinct row u

@@ -426,10 +426,13 @@ __device__ __forceinline__ float4 f4add(float4 a, float4 b) {
   return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
 }
 
-__global__ __launch_bounds__(FIX_THREADS) void segsum_fix_kernel(int64_t w4, const int32_t* __restrict__ seg_off,
-                                                                 const int32_t* __restrict__ counts,
-                                                                 const float4* __restrict__ part,
-                                                                 float* __restrict__ dst, int64_t ldd) {
+// The body as workgroup `bid` of `nblk` (a whole workgroup of FIX_THREADS): segsum_fix_kernel's
+// launch of its own, or the first workgroups of segsum_fix_zero_kernel's.
+__device__ __forceinline__ void segsum_fix_body(const int bid, const int nblk, int64_t w4,
+                                                const int32_t* __restrict__ seg_off,
+                                                const int32_t* __restrict__ counts,
+                                                const float4* __restrict__ part, float* __restrict__ dst,
+                                                int64_t ldd) {
   __shared__ float4 acc_s[FIX_THREADS];
   __shared__ int32_t todo_w[FIX_THREADS], todo_b[FIX_THREADS];
   __shared__ int32_t nw_todo, nb_todo;
@@ -439,11 +442,11 @@ __global__ __launch_bounds__(FIX_THREADS) void segsum_fix_kernel(int64_t w4, con
   const int64_t gw = w4 < FIX_THREADS ? w4 : FIX_THREADS;
   const int g = (int)(tid / gw);
   const int64_t j0 = tid - (int64_t)g * gw;
-  for (int64_t c0 = 0; c0 < Up; c0 += (int64_t)gridDim.x * FIX_THREADS) {
+  for (int64_t c0 = 0; c0 < Up; c0 += (int64_t)nblk * FIX_THREADS) {
     if (tid == 0) nw_todo = nb_todo = 0;
     __syncthreads();
     {
-      const int64_t u = c0 + (int64_t)tid * gridDim.x + blockIdx.x;
+      const int64_t u = c0 + (int64_t)tid * nblk + bid;
       if (u < Up) {
         bool wave_item = false, block_item = false;
         if (u >= U) {
@@ -518,6 +521,13 @@ __global__ __launch_bounds__(FIX_THREADS) void segsum_fix_kernel(int64_t w4, con
   }
 }
 
+__global__ __launch_bounds__(FIX_THREADS) void segsum_fix_kernel(int64_t w4, const int32_t* __restrict__ seg_off,
+                                                                 const int32_t* __restrict__ counts,
+                                                                 const float4* __restrict__ part,
+                                                                 float* __restrict__ dst, int64_t ldd) {
+  segsum_fix_body((int)blockIdx.x, (int)gridDim.x, w4, seg_off, counts, part, dst, ldd);
+}
+
 }  // namespace
 
 extern "C" int nr_unique_rows(const int64_t* ids, int64_t T, int64_t V, int64_t fill_row, const void* grad_mask,
@@ -556,16 +566,20 @@ namespace {
 // rows per workgroup: 16 -> 7.5 us for the bench batch's word-table gradient, 11.6 us at 64 (8: 7.7, 32:
 // 7.7; profiles/r05_af_ab_zero_absent_rows.json)
 constexpr int ZA_ROWS = 16;
-__global__ __launch_bounds__(256) void zero_absent_kernel(const int32_t* __restrict__ pos, const int32_t* __restrict__ counts,
-                                                          int64_t V, int64_t pad_row, float* __restrict__ dst, int64_t ldd,
-                                                          int64_t w4, uint8_t* __restrict__ flags) {
+constexpr int ZA_THREADS = 256;
+// The body as workgroup `bid`, run by threads 0 .. ZA_THREADS - 1 (a wider workgroup's other threads
+// must have left before the call: the barrier below is the workgroup's).
+__device__ __forceinline__ void zero_absent_body(const int64_t bid, const int32_t* __restrict__ pos,
+                                                 const int32_t* __restrict__ counts, int64_t V, int64_t pad_row,
+                                                 float* __restrict__ dst, int64_t ldd, int64_t w4,
+                                                 uint8_t* __restrict__ flags) {
   // flags (optional): 1 for a row the dgrad stores, 0 for one zeroed here (Adam's per-row
   // "gradient may be non-zero" flags)
   // ZA_ROWS rows per workgroup: the first ZA_ROWS lanes test them (coalesced scan reads) and list the
   // absent ones in LDS, then the workgroup zeroes the listed rows together
   __shared__ int32_t rows[ZA_ROWS];
   __shared__ int nrow;
-  const int64_t v0 = (int64_t)blockIdx.x * ZA_ROWS;
+  const int64_t v0 = bid * ZA_ROWS;
   if (threadIdx.x < 64) {
     const int64_t v = v0 + threadIdx.x;
     bool absent = false;
@@ -580,16 +594,53 @@ __global__ __launch_bounds__(256) void zero_absent_kernel(const int32_t* __restr
   }
   __syncthreads();
   const int n = nrow, n4 = (int)w4;
-  for (int e = threadIdx.x; e < n * n4; e += 256) {
+  for (int e = threadIdx.x; e < n * n4; e += ZA_THREADS) {
     const int r = e / n4;
     reinterpret_cast<float4*>(dst + (v0 + rows[r]) * ldd)[e - r * n4] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
 }
+
+__global__ __launch_bounds__(ZA_THREADS) void zero_absent_kernel(const int32_t* __restrict__ pos,
+                                                                 const int32_t* __restrict__ counts, int64_t V,
+                                                                 int64_t pad_row, float* __restrict__ dst, int64_t ldd,
+                                                                 int64_t w4, uint8_t* __restrict__ flags) {
+  zero_absent_body((int64_t)blockIdx.x, pos, counts, V, pad_row, dst, ldd, w4, flags);
+}
+
+// The segment sum's fix-up pass and the zero fill in one launch: workgroups [0, fix_blocks) are
+// segsum_fix_kernel's grid, the rest zero_absent_kernel's.  The two roles share nothing (the zero
+// fill reads the distinct-row scan, the fix-up the pieces of pass 1) and no workgroup waits for
+// another.  A zero-fill workgroup's threads past ZA_THREADS leave before that role's barrier, so
+// neither role's barrier is ever reached by a part of the waves still alive in its workgroup.
+struct ZeroAbsentArgs {
+  const int32_t* pos;
+  int64_t V, pad_row;
+  float* dst;
+  int64_t ldd, w4;
+  uint8_t* flags;
+};
+static_assert(FIX_THREADS >= ZA_THREADS, "the fused launch is FIX_THREADS wide");
+__global__ __launch_bounds__(FIX_THREADS) void segsum_fix_zero_kernel(int fix_blocks, int64_t w4,
+                                                                      const int32_t* __restrict__ seg_off,
+                                                                      const int32_t* __restrict__ counts,
+                                                                      const float4* __restrict__ part,
+                                                                      float* __restrict__ dst, int64_t ldd,
+                                                                      ZeroAbsentArgs z) {
+  if ((int)blockIdx.x < fix_blocks) {
+    segsum_fix_body((int)blockIdx.x, fix_blocks, w4, seg_off, counts, part, dst, ldd);
+    return;
+  }
+  if (threadIdx.x >= ZA_THREADS) return;
+  zero_absent_body((int64_t)blockIdx.x - fix_blocks, z.pos, counts, z.V, z.pad_row, z.dst, z.ldd, z.w4, z.flags);
+}
 }  // namespace
 
-extern "C" int nr_unique_rows_zero_absent(const int32_t* work, const int32_t* counts, int64_t V, int64_t pad_row,
-                                          float* dst, int64_t ldd, int64_t width, uint8_t* flags,
-                                          hipStream_t stream) {
+namespace {
+// nr_unique_rows_zero_absent's argument checks; `z`: the kernel's view of a call that has work to do
+// (z.pos null: nothing to do)
+int zero_absent_args(const int32_t* work, const int32_t* counts, int64_t V, int64_t pad_row, float* dst, int64_t ldd,
+                     int64_t width, uint8_t* flags, ZeroAbsentArgs& z) {
+  z = ZeroAbsentArgs{nullptr, V, pad_row, dst, ldd, width / 4, flags};
   if (V < 1 || V > 0x7fffffff || width < 0 || width > (int64_t)(0x7fffffff / 64) * 4 || (width & 3) || (ldd & 3) ||
       ldd < width)
     return NR_EINVAL(0);
@@ -597,9 +648,20 @@ extern "C" int nr_unique_rows_zero_absent(const int32_t* work, const int32_t* co
   if (reinterpret_cast<uintptr_t>(dst) & 15) return NR_EINVAL(2);
   if (width == 0 && !flags) return NR_OK;
   const int64_t V4 = (V + 3) & ~int64_t(3);
-  const int32_t* pos = work + CTRL_WORDS + 3 * V4;
-  hipLaunchKernelGGL(zero_absent_kernel, dim3((unsigned)((V + ZA_ROWS - 1) / ZA_ROWS)), dim3(256), 0, stream, pos, counts, V, pad_row,
-                     dst, ldd, width / 4, flags);
+  z.pos = work + CTRL_WORDS + 3 * V4;
+  return NR_OK;
+}
+unsigned zero_absent_blocks(int64_t V) { return (unsigned)((V + ZA_ROWS - 1) / ZA_ROWS); }
+}  // namespace
+
+extern "C" int nr_unique_rows_zero_absent(const int32_t* work, const int32_t* counts, int64_t V, int64_t pad_row,
+                                          float* dst, int64_t ldd, int64_t width, uint8_t* flags,
+                                          hipStream_t stream) {
+  ZeroAbsentArgs z;
+  const int rc = zero_absent_args(work, counts, V, pad_row, dst, ldd, width, flags, z);
+  if (rc != NR_OK || !z.pos) return rc;
+  hipLaunchKernelGGL(zero_absent_kernel, dim3(zero_absent_blocks(V)), dim3(ZA_THREADS), 0, stream, z.pos, counts, V,
+                     pad_row, dst, ldd, z.w4, flags);
   NR_LAUNCH_CHECK();
   return NR_OK;
 }
@@ -616,8 +678,17 @@ extern "C" int64_t nr_segment_rows_sum_workspace(int64_t T, int64_t width) {
 namespace {
 int segsum_launch(bool taps, const float* src, int64_t lds, int64_t width, int64_t wt4, int L, int64_t T,
                   const int32_t* seg_off, const int32_t* seg_tok, const int32_t* seg_of, const int32_t* counts,
-                  int64_t rows_max, float* work, float* dst, int64_t ldd, hipStream_t stream, int skip_single = 0) {
-  if (rows_max == 0 || width == 0) return NR_OK;
+                  int64_t rows_max, float* work, float* dst, int64_t ldd, hipStream_t stream, int skip_single = 0,
+                  const ZeroAbsentArgs* z = nullptr) {
+  // z (a zero fill with work to do, zero_absent_args): its workgroups behind the fix-up's, one launch
+  if (rows_max == 0 || width == 0) {
+    if (z) {
+      hipLaunchKernelGGL(zero_absent_kernel, dim3(zero_absent_blocks(z->V)), dim3(ZA_THREADS), 0, stream, z->pos,
+                         counts, z->V, z->pad_row, z->dst, z->ldd, z->w4, z->flags);
+      NR_LAUNCH_CHECK();
+    }
+    return NR_OK;
+  }
   const int64_t w4 = width / 4;
   if (T > 0) {
     const dim3 grid((unsigned)((T + SEG_RANGE - 1) / SEG_RANGE));
@@ -630,8 +701,14 @@ int segsum_launch(bool taps, const float* src, int64_t lds, int64_t width, int64
                          seg_of, counts, reinterpret_cast<float4*>(work), dst, ldd, skip_single);
   }
   const int64_t fb = (rows_max + 255) / 256;   // a quarter of each workgroup's threads hold a row
-  hipLaunchKernelGGL(segsum_fix_kernel, dim3((unsigned)(fb < FIX_BLOCKS ? fb : FIX_BLOCKS)), dim3(FIX_THREADS), 0,
-                     stream, w4, seg_off, counts, reinterpret_cast<const float4*>(work), dst, ldd);
+  const unsigned fix_blocks = (unsigned)(fb < FIX_BLOCKS ? fb : FIX_BLOCKS);
+  if (z)
+    hipLaunchKernelGGL(segsum_fix_zero_kernel, dim3(fix_blocks + zero_absent_blocks(z->V)), dim3(FIX_THREADS), 0,
+                       stream, (int)fix_blocks, w4, seg_off, counts, reinterpret_cast<const float4*>(work), dst, ldd,
+                       *z);
+  else
+    hipLaunchKernelGGL(segsum_fix_kernel, dim3(fix_blocks), dim3(FIX_THREADS), 0, stream, w4, seg_off, counts,
+                       reinterpret_cast<const float4*>(work), dst, ldd);
   NR_LAUNCH_CHECK();
   return NR_OK;
 }
@@ -658,6 +735,22 @@ extern "C" int nr_segment_rows_sum_multi(const float* src, int64_t lds, int64_t 
   if (misaligned(src) || misaligned(dst) || misaligned(work)) return NR_EINVAL(2);
   return segsum_launch(false, src, lds, width, 0, 1, T, seg_off, seg_tok, seg_of, counts, rows_max, work, dst, ldd,
                        stream, 1);
+}
+
+extern "C" int nr_segment_rows_sum_multi_zero(const float* src, int64_t lds, int64_t width, int64_t T,
+                                              const int32_t* seg_off, const int32_t* seg_tok, const int32_t* seg_of,
+                                              const int32_t* counts, int64_t rows_max, float* work, float* dst,
+                                              int64_t ldd, const int32_t* uwork, int64_t V, int64_t pad_row,
+                                              float* zdst, int64_t zldd, int64_t zwidth, uint8_t* flags,
+                                              hipStream_t stream) {
+  if (width < 0 || (width & 3) || (lds & 3) || (ldd & 3) || rows_max < 0 || T < 0) return NR_EINVAL(0);
+  if (!src || !seg_off || !seg_tok || !seg_of || !counts || !dst || (T > 0 && !work)) return NR_EINVAL(1);
+  if (misaligned(src) || misaligned(dst) || misaligned(work)) return NR_EINVAL(2);
+  ZeroAbsentArgs z;
+  const int rc = zero_absent_args(uwork, counts, V, pad_row, zdst, zldd, zwidth, flags, z);
+  if (rc != NR_OK) return rc;
+  return segsum_launch(false, src, lds, width, 0, 1, T, seg_off, seg_tok, seg_of, counts, rows_max, work, dst, ldd,
+                       stream, 1, z.pos ? &z : nullptr);
 }
 
 extern "C" int nr_segment_rows_sum_conv3(const float* src, int64_t lds, int64_t tap_width, int32_t L, int64_t T,

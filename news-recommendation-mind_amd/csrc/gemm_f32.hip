@@ -312,10 +312,14 @@ int launch_generic(const GemmCall& c, const nrfast::GemmRoute& r) {
 // The one entry behind the four exported ones: validates, routes (gemm_route.h), launches.
 // `dyn`: the dynamic form -- device-resident extents and / or a CU cap, fast kernels only; the static
 // form also takes unaligned operands (generic kernel) and small tiles.
-int gemm_entry(bool dyn, int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C,
-               int64_t ldc, const float* bias, int32_t epilogue, const nr_operand* c_rows, int64_t pad_row,
-               int32_t split_k, const int32_t* m_dev, const int32_t* k_dev, int32_t prec, int32_t max_cus, float* work,
-               int64_t work_elems, float* colsum, int32_t* colsum_folded, hipStream_t stream) {
+// gemm_prepare validates and routes (`run` false: a valid call with nothing to do), gemm_launch runs
+// the route; nr_gemm_f32_pair prepares two calls before it launches either.
+int gemm_prepare(bool dyn, int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C,
+                 int64_t ldc, const float* bias, int32_t epilogue, const nr_operand* c_rows, int64_t pad_row,
+                 int32_t split_k, const int32_t* m_dev, const int32_t* k_dev, int32_t prec, int32_t max_cus, float* work,
+                 int64_t work_elems, float* colsum, int32_t* colsum_folded, hipStream_t stream, GemmCall& c,
+                 nrfast::GemmRoute& r, bool& run) {
+  run = false;
   if (work_elems < 0 || (work_elems > 0 && !work)) return NR_EINVAL(16);
   if (colsum_folded) *colsum_folded = 0;
   if (colsum && !colsum_folded) return NR_EINVAL(17);
@@ -347,13 +351,36 @@ int gemm_entry(bool dyn, int64_t M, int64_t N, int64_t K, const nr_operand* A, c
   if (M == 0 || N == 0 || (dyn && K == 0)) return NR_OK;
   if (no_store_rows) return NR_EINVAL(4);
 
-  GemmCall c{{M, N, K, A, B, c_rows, epilogue, split_k, prec, dyn, m_dev != nullptr, max_cus, work, work_elems,
-              colsum != nullptr},
-             C, ldc, bias, pad_row, m_dev, k_dev, work, colsum, colsum_folded, stream};
+  c = GemmCall{{M, N, K, A, B, c_rows, epilogue, split_k, prec, dyn, m_dev != nullptr, max_cus, work, work_elems,
+                colsum != nullptr},
+               C, ldc, bias, pad_row, m_dev, k_dev, work, colsum, colsum_folded, stream};
   // the CU count matters to a route only where it sizes a workspace's use
-  const nrfast::GemmRoute r = nrfast::gemm_route(c.p, work ? nr_gemm_device_cus() : 0);
+  r = nrfast::gemm_route(c.p, work ? nr_gemm_device_cus() : 0);
   if (r.family == nrfast::GEMM_NOT_ELIGIBLE) return NR_EINVAL(r.einval);
+  run = true;
+  return NR_OK;
+}
+
+int gemm_launch(const GemmCall& c, const nrfast::GemmRoute& r) {
   return r.family == nrfast::GEMM_GENERIC ? launch_generic(c, r) : nr_gemm_fast(c, r);
+}
+
+int gemm_entry(bool dyn, int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C,
+               int64_t ldc, const float* bias, int32_t epilogue, const nr_operand* c_rows, int64_t pad_row,
+               int32_t split_k, const int32_t* m_dev, const int32_t* k_dev, int32_t prec, int32_t max_cus, float* work,
+               int64_t work_elems, float* colsum, int32_t* colsum_folded, hipStream_t stream) {
+  GemmCall c;
+  nrfast::GemmRoute r;
+  bool run;
+  const int rc = gemm_prepare(dyn, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec,
+                              max_cus, work, work_elems, colsum, colsum_folded, stream, c, r, run);
+  return rc != NR_OK || !run ? rc : gemm_launch(c, r);
+}
+
+int desc_prepare(const nr_gemm_desc* d, hipStream_t stream, GemmCall& c, nrfast::GemmRoute& r, bool& run) {
+  return gemm_prepare(d->m_dev || d->k_dev || d->max_cus != 0, d->M, d->N, d->K, d->A, d->B, d->C, d->ldc, d->bias,
+                      d->epilogue, d->c_rows, d->pad_row, d->split_k, d->m_dev, d->k_dev, d->prec, d->max_cus, d->work,
+                      d->work_elems, d->colsum, d->colsum_folded, stream, c, r, run);
 }
 
 }  // namespace
@@ -374,6 +401,28 @@ extern "C" int nr_gemm_f32_ws(int64_t M, int64_t N, int64_t K, const nr_operand*
                               int32_t* colsum_folded, hipStream_t stream) {
   return gemm_entry(m_dev || k_dev || max_cus != 0, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k,
                     m_dev, k_dev, prec, max_cus, work, work_elems, colsum, colsum_folded, stream);
+}
+
+// Two independent problems: one launch where gemm_pair_order (gemm_route.h) allows it, else the two
+// calls of nr_gemm_f32_ws one after the other.  Both are validated before either launches.
+extern "C" int nr_gemm_f32_pair(const nr_gemm_desc* p1, const nr_gemm_desc* p2, hipStream_t stream) {
+  if (!p1 || !p2) return NR_EINVAL(200);
+  GemmCall c1, c2;
+  nrfast::GemmRoute r1, r2;
+  bool run1, run2;
+  int rc = desc_prepare(p1, stream, c1, r1, run1);
+  if (rc != NR_OK) return rc;
+  rc = desc_prepare(p2, stream, c2, r2, run2);
+  if (rc != NR_OK) return rc <= -1000 ? rc - 100 : rc;   // NR_EINVAL(100 + n): problem 2's argument n
+  if (run1 && run2) {
+    const nrfast::GemmOut o1{c1.C, c1.ldc, c1.bias}, o2{c2.C, c2.ldc, c2.bias};
+    if (nrfast::gemm_pair_alias(c1.p, o1, c2.p, o2)) return NR_EINVAL(201);
+    const int order = nrfast::gemm_pair_order(c1.p, r1, o1, c2.p, r2, o2);
+    if (order == 1) return nr_gemm_fast_pair(c1, r1, c2, r2);
+    if (order == 2) return nr_gemm_fast_pair(c2, r2, c1, r1);
+  }
+  if (run1 && (rc = gemm_launch(c1, r1)) != NR_OK) return rc;
+  return run2 ? gemm_launch(c2, r2) : NR_OK;
 }
 
 // Device-resident extents: M and K are upper bounds (grid sizing); the kernel reads the actual

@@ -19,3 +19,5 @@ struct GemmCall {
 int nr_gemm_device_cus();
 // Launches a GEMM_F32_64 / F32_128 / SPLIT_128 / BIG route, and the reductions it asks for.
 int nr_gemm_fast(const GemmCall& c, const nrfast::GemmRoute& r);
+// Launches two GEMM_F32_64 routes as one kernel: (a, b) in the order of nrfast::pair_modes.
+int nr_gemm_fast_pair(const GemmCall& a, const nrfast::GemmRoute& ra, const GemmCall& b, const nrfast::GemmRoute& rb);

@@ -132,7 +132,9 @@ extern "C" int64_t nr_gemm_splitk_workspace(void) {
 
 int nr_gemm_device_cus() { return nrfast::device_cus(); }
 
-int nr_gemm_fast(const GemmCall& c, const nrfast::GemmRoute& r) {
+namespace {
+// the kernel arguments of a routed call
+nrfast::Args make_args(const GemmCall& c, const nrfast::GemmRoute& r) {
   using namespace nrfast;
   const GemmProblem& p = c.p;
   const nr_operand *A = p.A, *B = p.B, *cr = p.c_rows;
@@ -162,6 +164,21 @@ int nr_gemm_fast(const GemmCall& c, const nrfast::GemmRoute& r) {
     g.slab_stride = p.M * sld;
     g.colsum = r.fold ? c.colsum : nullptr;
   }
+  return g;
+}
+}  // namespace
+
+int nr_gemm_fast_pair(const GemmCall& a, const nrfast::GemmRoute& ra, const GemmCall& b, const nrfast::GemmRoute& rb) {
+  if (ra.family != nrfast::GEMM_F32_64 || rb.family != nrfast::GEMM_F32_64 || !nrfast::pair_modes(ra, rb))
+    return NR_EINVAL(7);
+  return nrfast::launch_pair64(make_args(a, ra), make_args(b, rb), a.stream);
+}
+
+int nr_gemm_fast(const GemmCall& c, const nrfast::GemmRoute& r) {
+  using namespace nrfast;
+  const GemmProblem& p = c.p;
+  const Args g = make_args(c, r);
+  const int64_t sld = (p.N + 3) & ~int64_t(3);
   int rc;
   switch (r.family) {
     case GEMM_F32_64: return launch_modes64(g, r, c.stream);

@@ -643,6 +643,7 @@ int launch_persistent(Kern kern, const Args& g, hipStream_t s) {
 // the launch tables of the other translation units (each returns NR_EINVAL(7) for a combination it
 // does not instantiate; gemm_route never routes one there)
 int launch_modes64(const Args& g, const GemmRoute& r, hipStream_t s);     // gemm_fast64.hip
+int launch_pair64(const Args& a, const Args& b, hipStream_t s);           // gemm_fast64.hip: two problems, one launch
 int launch_split_kc1(const Args& g, const GemmRoute& r, hipStream_t s);   // gemm_split_{kc,mn}{1,3}.hip: K- or
 int launch_split_kc3(const Args& g, const GemmRoute& r, hipStream_t s);   // MN-contiguous A, 1 or 3 planes
 int launch_split_mn1(const Args& g, const GemmRoute& r, hipStream_t s);

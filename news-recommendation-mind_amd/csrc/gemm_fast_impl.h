@@ -16,12 +16,15 @@ namespace nrfast {
 // next unit's first tiles load during the current unit's last ones, and the finished unit's
 // epilogue stores go out behind them.  A grid of `units` blocks is the plain one-tile-per-block
 // kernel.
+// The body takes its place in the grid as arguments (`bid` of `G` workgroups, the LDS images from the
+// caller), so that one launch can run two problems side by side (gemm_fast_pair_kernel): each problem
+// sees a grid of its own and walks its units in the order it has alone.
 template <int BM, int BN, int AM, int BMODE, bool TR>
-__global__ __launch_bounds__(256, 2) void gemm_fast_kernel(Args g) {
+__device__ __forceinline__ void gemm_fast_body(Args g, const int bid, const int G,
+                                               float (*As)[Loader<BM, AM>::LDS_FLOATS],
+                                               float (*Bs)[Loader<BN, BMODE>::LDS_FLOATS]) {
   using LA = Loader<BM, AM>;
   using LB = Loader<BN, BMODE>;
-  __shared__ __attribute__((aligned(16))) float As[2][LA::LDS_FLOATS];
-  __shared__ __attribute__((aligned(16))) float Bs[2][LB::LDS_FLOATS];
   constexpr bool IDX_AHEAD = AM == MN_GATHER || BMODE == MN_GATHER;
 
   // device-resident extents (row counts produced on the GPU, e.g. nr_unique_rows): the host
@@ -40,7 +43,6 @@ __global__ __launch_bounds__(256, 2) void gemm_fast_kernel(Args g) {
   const int gn = (int)((g.N + BN - 1) / BN);
   const int ntiles = (int)((g.M + BM - 1) / BM) * gn;
   const int units = ntiles * g.splits;
-  const int G = gridDim.x;
 
   // first non-empty unit at or after virtual id `id` in this block's sequence (a split past a
   // device-resident K is empty), or `units`
@@ -71,7 +73,7 @@ __global__ __launch_bounds__(256, 2) void gemm_fast_kernel(Args g) {
 
   Cursor cp;   // compute position
   cp.kt = 0;
-  cp.id = skip_empty(blockIdx.x, cp.u);
+  cp.id = skip_empty(bid, cp.u);
   if (cp.id >= units) return;
 
   constexpr int TI = BM / 64, TJ = BN / 64;
@@ -179,6 +181,13 @@ __global__ __launch_bounds__(256, 2) void gemm_fast_kernel(Args g) {
     }
   }
   epilogue_any<TR, TI, TJ>(g, acc, cp.u.m0, cp.u.n0, wm, wn, h, c);
+}
+
+template <int BM, int BN, int AM, int BMODE, bool TR>
+__global__ __launch_bounds__(256, 2) void gemm_fast_kernel(Args g) {
+  __shared__ __attribute__((aligned(16))) float As[2][Loader<BM, AM>::LDS_FLOATS];
+  __shared__ __attribute__((aligned(16))) float Bs[2][Loader<BN, BMODE>::LDS_FLOATS];
+  gemm_fast_body<BM, BN, AM, BMODE, TR>(g, (int)blockIdx.x, (int)gridDim.x, As, Bs);
 }
 
 template <int BM, int BN>

@@ -257,4 +257,87 @@ inline GemmRoute gemm_route(const GemmProblem& p, int cus) {
   return r;
 }
 
+// ---- two independent problems in one launch (nr_gemm_f32_pair)
+
+// Where a problem's result goes (not part of routing: GemmProblem has no output).
+struct GemmOut {
+  const float* C;
+  int64_t ldc;
+  const float* bias;
+};
+
+// Bytes [lo, hi) of a stored matrix of `rows` x `cols` floats, rows `ld` apart (empty: lo == hi == 0).
+struct ByteSpan {
+  uintptr_t lo, hi;
+};
+inline ByteSpan span_of(const float* p, int64_t rows, int64_t ld, int64_t cols) {
+  if (!p || rows <= 0 || cols <= 0) return {0, 0};
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+  return {lo, lo + (uintptr_t)(((rows - 1) * ld + cols) * (int64_t)sizeof(float))};
+}
+inline bool spans_overlap(ByteSpan a, ByteSpan b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// The stored bytes an operand reads: a plain one's [extent x K] (K-contiguous) or [K x extent]
+// (MN-contiguous) matrix; a gathered / conv3 one's table has no height known here -- its first row.
+inline ByteSpan operand_span(const nr_operand* o, int64_t extent, int64_t K) {
+  if (!o) return {0, 0};
+  const bool kc = o->layout == NR_KCONTIG;
+  const int64_t rows = o->map != NR_ROWS_PLAIN ? 1 : (kc ? extent : K);
+  return span_of(o->data, rows, o->ld, kc ? K : extent);
+}
+
+// Does either problem's output ([M x N] at C, rows ldc apart) overlap what the other problem reads
+// (A, B, the auxiliary matrix of the gate / GELU epilogues, bias) or writes?  Such problems are not
+// independent: nr_gemm_f32_pair refuses them.
+inline bool gemm_pair_alias(const GemmProblem& p1, const GemmOut& o1, const GemmProblem& p2, const GemmOut& o2) {
+  const ByteSpan c1 = span_of(o1.C, p1.M, o1.ldc, p1.N), c2 = span_of(o2.C, p2.M, o2.ldc, p2.N);
+  if (spans_overlap(c1, c2)) return true;
+  auto reads = [](const GemmProblem& p, const GemmOut& o, ByteSpan c) {
+    const bool aux = p.c_rows && p.c_rows->data && p.c_rows->map == NR_ROWS_PLAIN;
+    return spans_overlap(c, operand_span(p.A, p.M, p.K)) || spans_overlap(c, operand_span(p.B, p.N, p.K)) ||
+           spans_overlap(c, span_of(o.bias, 1, p.N, p.N)) ||
+           (aux && spans_overlap(c, span_of(p.c_rows->data, p.M, p.c_rows->ld, p.N)));
+  };
+  return reads(p2, o2, c1) || reads(p1, o1, c2);
+}
+
+// The pairs gemm_fast64.hip instantiates, as (first, second): an input gradient dx = dY W (K-contiguous
+// x MN-contiguous, transposed accumulators) beside a weight gradient dW += dYᵀ x (MN x MN, C-major).
+inline bool pair_modes(const GemmRoute& a, const GemmRoute& b) {
+  return a.am == KC_PLAIN && a.bmode == MN_PLAIN && a.tr && b.am == MN_PLAIN && b.bmode == MN_PLAIN && !b.tr;
+}
+
+// Can two validated, routed problems share one launch?  0: no (they run one after the other); 1: yes, as
+// (p1, p2); 2: yes, as (p2, p1).  Both on the exact-f32 64 x 64 kernel in an instantiated mode pair,
+// static form (no device extents), no CU cap, outputs that alias nothing of the other problem.
+inline int gemm_pair_order(const GemmProblem& p1, const GemmRoute& r1, const GemmOut& o1, const GemmProblem& p2,
+                           const GemmRoute& r2, const GemmOut& o2) {
+  if (r1.family != GEMM_F32_64 || r2.family != GEMM_F32_64) return 0;
+  if (p1.dyn || p2.dyn || p1.max_cus != 0 || p2.max_cus != 0) return 0;
+  if (gemm_pair_alias(p1, o1, p2, o2)) return 0;
+  if (pair_modes(r1, r2)) return 1;
+  if (pair_modes(r2, r1)) return 2;
+  return 0;
+}
+
+
+// Workgroups of the pair launch for problems of ua and ub units on `slots` resident workgroups: each
+// problem its units when both fit, else the slots shared in proportion to the units (at least one
+// each); a's share is a multiple of 8 where it can be, so that no slot goes to an idle workgroup.
+inline void pair_grids(int64_t ua, int64_t ub, int slots, int& ga, int& off, int& gb) {
+  const int64_t pad = (ua + 7) / 8 * 8;
+  if (slots <= 0 || pad + ub <= slots) {
+    ga = (int)ua; off = (int)pad; gb = (int)ub;
+    return;
+  }
+  int64_t sb = slots * ub / (ua + ub);
+  if (sb < 1) sb = 1;
+  if (sb > ub) sb = ub;
+  int64_t sa = slots - sb;
+  if (sa > ua) sa = ua;
+  if (sa >= 8 && sa < ua) sa &= ~int64_t(7);
+  if (sa < 1) sa = 1;
+  ga = (int)sa; off = (int)((sa + 7) / 8 * 8); gb = (int)sb;
+}
+
 }  // namespace nrfast

@@ -37,6 +37,16 @@ class nr_operand(ctypes.Structure):
                 ("map", c_i32), ("seq_len", c_i32), ("seg", c_i32), ("layout", c_i32)]
 
 
+class nr_gemm_desc(ctypes.Structure):
+    """One nr_gemm_f32_ws call without its stream (nr_gemm_f32_pair takes two)."""
+    _fields_ = [("M", c_i64), ("N", c_i64), ("K", c_i64), ("A", ctypes.POINTER(nr_operand)),
+                ("B", ctypes.POINTER(nr_operand)), ("C", ctypes.c_void_p), ("ldc", c_i64), ("bias", ctypes.c_void_p),
+                ("epilogue", c_i32), ("c_rows", ctypes.POINTER(nr_operand)), ("pad_row", c_i64), ("split_k", c_i32),
+                ("m_dev", ctypes.c_void_p), ("k_dev", ctypes.c_void_p), ("prec", c_i32), ("max_cus", c_i32),
+                ("work", ctypes.c_void_p), ("work_elems", c_i64), ("colsum", ctypes.c_void_p),
+                ("colsum_folded", ctypes.POINTER(c_i32))]
+
+
 class nr_adam_tensor(ctypes.Structure):
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
                 ("exp_avg_sq", ctypes.c_void_p), ("n", c_i64), ("lr", c_f32), ("step", c_i64),
@@ -56,6 +66,7 @@ _SIGS = {
     "nr_gemm_f32_dyn": _GEMM + [c_ptr, c_ptr, c_i32, c_ptr],
     "nr_gemm_f32_dyn_cus": _GEMM + [c_ptr, c_ptr, c_i32, c_i32, c_ptr],
     "nr_gemm_f32_ws": _GEMM + [c_ptr, c_ptr, c_i32, c_i32, c_ptr, c_i64, c_ptr, ctypes.POINTER(c_i32), c_ptr],
+    "nr_gemm_f32_pair": [ctypes.POINTER(nr_gemm_desc), ctypes.POINTER(nr_gemm_desc), c_ptr],
     "nr_gemm_splitk_workspace": [],
     "nr_score_nll_fwd": [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr],
     "nr_score_nll_workspace": [c_i64],
@@ -67,6 +78,8 @@ _SIGS = {
                             c_ptr],
     "nr_segment_rows_sum_multi": [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
                                   c_ptr],
+    "nr_segment_rows_sum_multi_zero": [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr,
+                                       c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr],
     "nr_unique_rows_zero_absent": [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr],
     "nr_segment_rows_sum_workspace": [c_i64, c_i64],
     "nr_unique_rows_workspace": [c_i64],

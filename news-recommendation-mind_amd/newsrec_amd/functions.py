@@ -323,6 +323,11 @@ FUSED_SAVED_BWD = False
 # >= 512 k per piece.  One-box A/B of the NRMS step, interleaved rounds: unsplit 1.4206-1.4275 ms,
 # two pieces 1.4292 ms -- kept unsplit
 USER_DGRAD_SPLIT = 1
+# ... and that input gradient in ONE launch with the encoder's weight gradient (nr_gemm_f32_pair: both are
+# exact-f32 64 x 64 GEMMs of 150 and 324 units, each alone filling under two thirds of the 512 resident slots).
+# One-process A/B of the NRMS step, interleaved rounds: 1.2975 -> 1.2840 ms (37.7 us for 28.2 + 23.6;
+# profiles/r07_a_ab_step_switches.json)
+USER_GEMM_PAIR = True
 # CNN conv weight gradient: split-K partials through a workspace + one ordered reduction instead of
 # fp32 atomics (one-box A/B, graphed steps): configs[1] bf16 0.741 -> 0.700 ms; bf16x6 CNN + attention
 # 0.899 -> 0.860 ms, CNN + GRU 1.171 -> 1.126 ms
@@ -345,6 +350,9 @@ PROJ_DGRAD_TAIL_WS = True
 SINGLE_ROWS_DIRECT = True
 # the word-table gradient: only the rows absent from the batch (and the pad row) zero-filled
 ABSENT_ROWS_ZERO = True
+# ... by workgroups of the distinct-row segment sum's fix-up launch (nr_segment_rows_sum_multi_zero)
+# instead of a launch of their own (same A/B: -3 to -10 us per step over three sessions; 12.4 us for 8.6 + 7.1)
+SEGSUM_ZERO_FUSED = True
 # ... and those rows flagged for Adam, which then skips reading them (optim.FusedAdam, row_touched)
 WORD_ROW_FLAGS = True
 # CNN word attention (tanh key projection + learned-query pooling) fused per title, forward and
@@ -478,13 +486,16 @@ class _LocalRowGrad:
         self.flags.clear()
 
 
-def _zero_absent_word_rows(table, dtable, ur, pad_row):
+def _zero_absent_word_rows(table, dtable, ur, pad_row, segsum=None):
     """Zero dtable's rows of ids absent from the batch (and the pad row).  Returns Adam's per-row
     flags (1 = the dgrad stores the row) when the gradient will become ``table.grad`` as it is: a leaf
     table whose ``.grad`` is None (no accumulation into an older gradient) in a single process (a
-    dense all-reduce would add other ranks' rows).  None otherwise."""
+    dense all-reduce would add other ranks' rows).  None otherwise.  ``segsum`` = (src, dst): the
+    multi-token segment sum src -> dst runs with it, the zero fill inside its second launch."""
     track = WORD_ROW_FLAGS and _is_param_leaf(table) and table.grad is None and not _multi_rank()
     flags = torch.empty(dtable.shape[0], dtype=torch.uint8, device=dtable.device) if track else None
+    if segsum is not None:
+        return flags if ur.segment_sum_multi_zero(segsum[0], segsum[1], dtable, pad_row, flags) else None
     return flags if ur.zero_absent_rows(dtable, pad_row, flags) else None
 
 
@@ -652,13 +663,23 @@ class MHANewsFn(_GradAwareFn):
         if ur is not None:
             # per-distinct-row gradient, then the two GEMMs over U rows instead of T tokens
             dYu = dYall[T:]
-            if direct:
+            absent_only = (ctx.needs_input_grad[0] and PROJ_DGRAD_TAIL_WS and ABSENT_ROWS_ZERO and
+                           ctx.prec == L.GEMM_BF16X6 and 0 <= pad_row < V)
+            # the zero fill of the table gradient's absent rows depends on the distinct-row scan only:
+            # its workgroups run in the segment sum's fix-up launch (single process)
+            zero_in_segsum = SEGSUM_ZERO_FUSED and direct and absent_only and not _multi_rank()
+            if zero_in_segsum:
+                dtable = table_grad_buffer(ctx.table_ref, V, E, table.device, zero=False)
+                rflags = _zero_absent_word_rows(ctx.table_ref, dtable, ur, pad_row, segsum=(dY, dYu))
+            elif direct:
                 ur.segment_sum_multi(dY, dYu)
             else:
                 ur.segment_sum(dY, dYu)
             inflight = False
             if ctx.needs_input_grad[0]:
-                if PROJ_DGRAD_TAIL_WS and ABSENT_ROWS_ZERO and ctx.prec == L.GEMM_BF16X6 and 0 <= pad_row < V:
+                if zero_in_segsum:
+                    pass
+                elif absent_only:
                     # every present row is stored by the dgrad (its tail through the workspace, no
                     # atomics): zero only the absent rows and the pad row instead of the whole table
                     dtable = table_grad_buffer(ctx.table_ref, V, E, table.device, zero=False)
@@ -1026,6 +1047,14 @@ class MHAFn(_GradAwareFn):
             dx = torch.zeros(rows, D, device=dev)
             K.gemm(rows, D, NY, K.operand(dY, L.KCONTIG), K.operand(w_cat, L.MNCONTIG), dx, epilogue=L.EPI_ATOMIC,
                    split_k=split)
+        elif USER_GEMM_PAIR:
+            # dx = dY W and dW += dYᵀ x read the same dY and depend on nothing else: one launch
+            # (_proj_wgrad's GEMM without a bias gradient: db came from the attention backward)
+            dx = _grad_out(ctx.dx_dest, rows, D, x)
+            K.gemm_pair(K.gemm_desc(rows, D, NY, K.operand(dY, L.KCONTIG), K.operand(w_cat, L.MNCONTIG), dx),
+                        K.gemm_desc(NY, D, rows, K.operand(dY, L.MNCONTIG), K.operand(x, L.MNCONTIG), dw,
+                                    epilogue=L.EPI_ATOMIC, split_k=_split_k(NY, D, rows)), dx)
+            return dx, None, dw, db, None, None, None, None, None
         else:
             dx = _grad_out(ctx.dx_dest, rows, D, x)
             K.gemm(rows, D, NY, K.operand(dY, L.KCONTIG), K.operand(w_cat, L.MNCONTIG), dx)

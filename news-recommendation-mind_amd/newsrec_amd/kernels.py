@@ -93,6 +93,28 @@ def gemm(M, N, K, A, B, C, ldc=None, bias=None, epilogue=L.EPI_STORE, c_rows=Non
     return bool(folded.value)
 
 
+def gemm_desc(M, N, K, A, B, C, ldc=None, bias=None, epilogue=L.EPI_STORE, c_rows=None, pad_row=-1, split_k=1,
+              prec=None, max_cus=0):
+    """One problem of ``gemm_pair``: the arguments of ``gemm`` (no workspace, no column sums) as an
+    nr_gemm_desc.  The struct keeps its operands and tensors alive."""
+    _f32(C, bias)
+    if bias is not None and bias.numel() < N:
+        raise L.HipError("gemm_desc: bias has %d < N=%d entries" % (bias.numel(), N))
+    d = L.nr_gemm_desc(M, N, K, ctypes.pointer(A), ctypes.pointer(B), C.data_ptr(),
+                       ldc if ldc is not None else C.stride(0), bias.data_ptr() if bias is not None else None,
+                       epilogue, ctypes.pointer(c_rows) if c_rows is not None else None, pad_row, split_k, None, None,
+                       _prec(prec), int(max_cus), None, 0, None, None)
+    d._keep = (A, B, C, bias, c_rows)
+    return d
+
+
+def gemm_pair(d1, d2, like):
+    """Two independent GEMMs (``gemm_desc``) in one launch where the library can pair them
+    (nr_gemm_f32_pair: both on the exact-f32 64 x 64 kernel, an input gradient beside a weight
+    gradient), else one after the other; the results are those of two ``gemm`` calls either way."""
+    L.call("nr_gemm_f32_pair", ctypes.byref(d1), ctypes.byref(d2), L.stream_ptr(like))
+
+
 def _splitk_work(like):
     """Workspace of a split-K weight-gradient GEMM with its bias gradient folded in (nr_gemm_f32_ws:
     partial tiles and column sums through plain stores and one reduction); from the caching
@@ -295,6 +317,31 @@ class UniqueRows:
         L.call("nr_segment_rows_sum_multi", L.ptr(src), src.stride(0), width, self.T, L.ptr(self.seg_off),
                L.ptr(self.seg_tok), L.ptr(self.seg_of), L.ptr(self.counts), self.cap, L.ptr(work), L.ptr(dst),
                dst.stride(0), L.stream_ptr(src))
+
+    def segment_sum_multi_zero(self, src, dst, zdst, pad_row, flags=None):
+        """``segment_sum_multi(src, dst)`` and ``zero_absent_rows(zdst, pad_row, flags)`` with the zero
+        fill's workgroups in the segment sum's second launch (nr_segment_rows_sum_multi_zero).  Returns
+        what ``zero_absent_rows`` returns; the two plain calls run when this object's presence scan
+        has been replaced."""
+        if _UR_GEN.get(self._key) != self._gen:
+            self.segment_sum_multi(src, dst)
+            return self.zero_absent_rows(zdst, pad_row, flags)
+        _f32(src, dst, zdst)
+        _rows_ok(src, self.T, src.shape[1], "segment_sum src")
+        _rows_ok(dst, self.cap, src.shape[1], "segment_sum dst")
+        if zdst.dim() != 2 or zdst.shape[0] != self.vocab or zdst.stride(1) != 1:
+            raise L.HipError("zero_absent_rows: dst must be a row-major [vocab, W] matrix")
+        if flags is not None and (flags.dtype != torch.uint8 or flags.numel() != self.vocab or
+                                  not flags.is_contiguous() or flags.device != zdst.device):
+            raise L.HipError("zero_absent_rows: flags must be a contiguous uint8 [vocab] tensor on dst's device")
+        width = src.shape[1]
+        nbytes = L.load().nr_segment_rows_sum_workspace(self.T, width)
+        work = torch.empty(max(1, nbytes // 4), device=src.device, dtype=torch.float32)
+        L.call("nr_segment_rows_sum_multi_zero", L.ptr(src), src.stride(0), width, self.T, L.ptr(self.seg_off),
+               L.ptr(self.seg_tok), L.ptr(self.seg_of), L.ptr(self.counts), self.cap, L.ptr(work), L.ptr(dst),
+               dst.stride(0), L.ptr(self._work), self.vocab, int(pad_row), L.ptr(zdst), zdst.stride(0),
+               zdst.shape[1], L.ptr(flags) if flags is not None else None, L.stream_ptr(src))
+        return True
 
     def segment_sum_conv3(self, src, dst, tap_width, seq_len):
         """dst[u][tap*tap_width + c] = Σ src[t + 1 - tap][c] over the tokens t of distinct row u (taps

@@ -22,6 +22,8 @@ def main():
     ap.add_argument("variants", nargs="+")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warm-rounds", type=int, default=0,
+                    help="untimed rounds first (the process's first timed round runs ~5 %% slow: clocks, caches)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     feed = bench.DeviceFeed(dev, 1, 0)
@@ -42,7 +44,7 @@ def main():
         opt = bench.make_optim(model, capturable=True)
         steps[v] = bench.GraphedStep(model, opt, feed, None, 3)
     res = {v: [] for v in a.variants}
-    for r in range(a.rounds):
+    for r in range(-a.warm_rounds, a.rounds):
         for v in a.variants:
             st = steps[v]
             torch.cuda.synchronize()
@@ -50,7 +52,8 @@ def main():
             for i in range(a.steps):
                 st(i)
             torch.cuda.synchronize()
-            res[v].append((time.perf_counter() - t0) / a.steps * 1e3)
+            if r >= 0:
+                res[v].append((time.perf_counter() - t0) / a.steps * 1e3)
     print(json.dumps({v: {"ms_per_step": [round(x, 4) for x in ms], "min": round(min(ms), 4)} for v, ms in res.items()}))
 
 
