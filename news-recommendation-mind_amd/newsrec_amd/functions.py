@@ -310,60 +310,18 @@ class _Probe:
 
 PROBE = _Probe()
 
+# The three switches below exist only so that tests can select the comparison form; nothing else sets
+# them (the step A/Bs that are settled are listed in DESIGN.md, "Settled step A/Bs").
 # Distinct-row projection in the news towers (False projects every token row: the token-wise form
 # the parity tests compare it with; module attributes, not environment switches).
 DEDUP_ROWS = True
-# Training forward saves the attention output; the backward runs split (False: the fused backward
-# that recomputes the attention).
-SPLIT_BWD = True
-# With the saved attention output: one fused kernel per title (LN backward + every head's attention
-# backward, dO kept in LDS) instead of the split pair (dO through HBM)
-FUSED_SAVED_BWD = False
 # Split-K factor of the MHA user encoder's input gradient (dx = dY [Wk; Wv], K = 1152); a split keeps
 # >= 512 k per piece.  One-box A/B of the NRMS step, interleaved rounds: unsplit 1.4206-1.4275 ms,
 # two pieces 1.4292 ms -- kept unsplit
 USER_DGRAD_SPLIT = 1
-# ... and that input gradient in ONE launch with the encoder's weight gradient (nr_gemm_f32_pair: both are
-# exact-f32 64 x 64 GEMMs of 150 and 324 units, each alone filling under two thirds of the 512 resident slots).
-# One-process A/B of the NRMS step, interleaved rounds: 1.2975 -> 1.2840 ms (37.7 us for 28.2 + 23.6;
-# profiles/r07_a_ab_step_switches.json)
-USER_GEMM_PAIR = True
-# CNN conv weight gradient: split-K partials through a workspace + one ordered reduction instead of
-# fp32 atomics (one-box A/B, graphed steps): configs[1] bf16 0.741 -> 0.700 ms; bf16x6 CNN + attention
-# 0.899 -> 0.860 ms, CNN + GRU 1.171 -> 1.126 ms
-WGRAD_WS_BF16 = True
-WGRAD_WS_BF16X6 = True
-# CNN table dgrad with the conv weights transposed to k-contiguous (one 1.5 MB copy per step):
-# one-box A/B of the graphed legs, bf16 0.698 -> 0.657 ms, fp32-class 0.851 -> 0.842 ms
-CNN_DGRAD_KC = True
-# NRMS table dgrad with the joint projection weight transposed to k-contiguous (one 3.5 MB copy per step),
-# so both operands take the K-contiguous loaders (and the interleaved split-stores) instead of the
-# MN-contiguous weight loader
-PROJ_DGRAD_KC = False
-# the NRMS projection weight gradient on the same workspace path: one process, interleaved rounds,
-# 1.459 -> 1.446 ms per NRMS step (round 2 measured it slower, before the bf16x6 units lost SLP)
-PROJ_WGRAD_WS = True
-# the table dgrad's stream-K tail through the GEMM workspace + an ordered reduction (no fp32 atomics)
-PROJ_DGRAD_TAIL_WS = True
-# the MHA news backward writes the gradient row of a token alone in its distinct row's segment
-# straight into the per-distinct-row sums (the segment sum then covers the rows of 2+ tokens)
-SINGLE_ROWS_DIRECT = True
-# the word-table gradient: only the rows absent from the batch (and the pad row) zero-filled
-ABSENT_ROWS_ZERO = True
-# ... by workgroups of the distinct-row segment sum's fix-up launch (nr_segment_rows_sum_multi_zero)
-# instead of a launch of their own (same A/B: -3 to -10 us per step over three sessions; 12.4 us for 8.6 + 7.1)
-SEGSUM_ZERO_FUSED = True
-# ... and those rows flagged for Adam, which then skips reading them (optim.FusedAdam, row_touched)
-WORD_ROW_FLAGS = True
 # CNN word attention (tanh key projection + learned-query pooling) fused per title, forward and
 # backward (nr_cnn_keypool_*; False: the key GEMM + pooling kernels the parity tests compare with).
 FUSED_KEYPOOL = True
-# The fused key-pool forward stores K = tanh(C Wqᵀ + bq) ([T, Hp], 34 MB at B = 32) and its backward
-# reads it instead of recomputing the key products per title (False: recomputed, K stays on chip)
-KEYPOOL_SAVE_K = True
-
-
-
 
 
 class _TableGradHook:
@@ -492,7 +450,7 @@ def _zero_absent_word_rows(table, dtable, ur, pad_row, segsum=None):
     table whose ``.grad`` is None (no accumulation into an older gradient) in a single process (a
     dense all-reduce would add other ranks' rows).  None otherwise.  ``segsum`` = (src, dst): the
     multi-token segment sum src -> dst runs with it, the zero fill inside its second launch."""
-    track = WORD_ROW_FLAGS and _is_param_leaf(table) and table.grad is None and not _multi_rank()
+    track = _is_param_leaf(table) and table.grad is None and not _multi_rank()
     flags = torch.empty(dtable.shape[0], dtype=torch.uint8, device=dtable.device) if track else None
     if segsum is not None:
         return flags if ur.segment_sum_multi_zero(segsum[0], segsum[1], dtable, pad_row, flags) else None
@@ -563,6 +521,45 @@ class _WgradDeferHook:
 WGRAD_DEFER_HOOK = _WgradDeferHook()
 
 
+def _word_table_grad(table, dYu, w_b, ur, pad_row, prec, bf16_store, segsum=None, probe=False):
+    """The word-table gradient of a distinct-row news tower: dtable[uids] = dYu w_b, one row per
+    distinct id of the batch (M = U, not U_pad: no duplicate pad ids), every other row zero.
+    dYu [cap, NK]: the per-distinct-row gradient sums; w_b: the weight operand [NK x E]; ``table``:
+    the tower's word-table argument (its hooks and row flags hang on it).
+
+    Where the dgrad stores every present row, only the absent rows and the pad row are zero-filled
+    instead of the whole table: under bf16x6 (the stream-K tail goes through the workspace, no
+    atomics) and, with ``bf16_store``, under bf16 as plain scatter stores (NR_EPI_SCATTER_STORE: no
+    atomic tail, which would need zeroed rows).  ``segsum`` = (dY, dYu): the multi-token segment sum
+    dY -> dYu is still to run; it runs here, with the zero fill's workgroups in its fix-up launch
+    where that fill is the absent-rows one (single process), before it otherwise.  ``probe``: the
+    dgrad launch is offered to PROBE as "proj_dgrad".
+
+    -> (dtable, inflight): TABLE_GRAD_HOOK may take the gradient (dtable None, inflight True: the
+    table's all-reduce then runs beside the weight gradient that follows)."""
+    V, E = table.shape
+    absent_only = 0 <= pad_row < V and (prec == L.GEMM_BF16X6 or (bf16_store and prec == L.GEMM_BF16))
+    epi = L.EPI_SCATTER_STORE if absent_only and prec == L.GEMM_BF16 else L.EPI_SCATTER_ZEROED
+    fold = segsum is not None and absent_only and not _multi_rank()
+    if segsum is not None and not fold:
+        ur.segment_sum_multi(*segsum)
+    dtable = table_grad_buffer(table, V, E, dYu.device, zero=not absent_only)
+    rflags = _zero_absent_word_rows(table, dtable, ur, pad_row, segsum if fold else None) if absent_only else None
+
+    def dgrad(dtable=dtable):   # bound now: the hook below may take the name's buffer
+        K.gemm_dyn(ur.cap, E, dYu.shape[1], K.operand(dYu, L.KCONTIG), w_b, dtable, m_dev=ur.n_rows,
+                   epilogue=epi, c_rows=K.rows_map(ur.uids, L.ROWS_GATHER), pad_row=pad_row, workspace=True)
+    if probe:
+        PROBE.run("proj_dgrad", dgrad, dtable, ur)
+    else:
+        dgrad()
+    inflight = TABLE_GRAD_HOOK(table, dtable)
+    if inflight:
+        dtable = None
+    _word_row_flags(table, dtable, rflags)
+    return dtable, inflight
+
+
 # ---------------------------------------------------------------------- MHA news encoder
 
 class MHANewsFn(_GradAwareFn):
@@ -602,8 +599,8 @@ class MHANewsFn(_GradAwareFn):
         tok = _empty(T, H, table) if want_tokens else None
         if fused:
             # attention + LN + dropout + pooling in one kernel per title; when a backward will
-            # run, the attention output O is saved too (the backward then skips recomputing it)
-            O = _empty(T, H, table) if SPLIT_BWD and _backward_possible(ctx) else None
+            # run, the attention output O is saved too (the split backward reads it instead of recomputing it)
+            O = _empty(T, H, table) if _backward_possible(ctx) else None
             # rng (device (seed, offset) snapshot) supersedes the host pair: kernel offset 0
             K.mha_pool_fwd(Y, mask, n, seq_len, heads, dk, dv, gamma, beta, query, news, stats, probs,
                            p_drop=p_drop, seed=seed, offset=0 if rng is not None else offset, zout=tok,
@@ -626,7 +623,6 @@ class MHANewsFn(_GradAwareFn):
     def backward(ctx, dnews, dtok):
         table, ids, mask, w_cat, gamma, beta, query, Y, O, probs, stats = ctx.saved_tensors
         _word_row_flags(ctx.table_ref, None, None)
-        rflags = None
         heads, dk, dv, seq_len, pad_row, p_drop, seed, offset, fused = ctx.cfg
         T = ids.numel()
         n = T // seq_len
@@ -638,14 +634,15 @@ class MHANewsFn(_GradAwareFn):
         dq, dgamma, dbeta, db, dw = _backward_zeros(ctx, table.device, (H,), (H,), (H,), (NY,), (NY, E))
         dz = dtok.contiguous() if dtok is not None else None
         ur = ctx.ur
-        # one buffer: per-token gradient rows [0, T), then the per-distinct-row sums [T, T + cap); with
-        # SINGLE_ROWS_DIRECT a token alone in its row's segment writes its row straight to the sums
-        direct = fused and ur is not None and SINGLE_ROWS_DIRECT
+        # one buffer: per-token gradient rows [0, T), then the per-distinct-row sums [T, T + cap); the fused
+        # backward writes the row of a token alone in its distinct row's segment straight to the sums
+        direct = fused and ur is not None
         dYall = _empty(T + (ur.cap if ur is not None else 0), NY, table)
         dY = dYall[:T]
+        # 1. pooling / LayerNorm / attention backward -> dY per token
         if fused:
             # split form: the LN pass's per-token row terms (the head pass rebuilds dO from O with them)
-            dob = torch.empty(T, 8, device=table.device) if O is not None and not FUSED_SAVED_BWD else None
+            dob = torch.empty(T, 8, device=table.device) if O is not None else None
             ws = _grad_copies(table.device, 3 * H + NY) if O is not None else None
             K.mha_pool_bwd(Y, mask, n, seq_len, heads, dk, dv, gamma, beta, query, stats, probs, dnews,
                            dYall if direct else dY, db, dq,
@@ -661,52 +658,28 @@ class MHANewsFn(_GradAwareFn):
                            dbias=db)
         dtable = None
         if ur is not None:
-            # per-distinct-row gradient, then the two GEMMs over U rows instead of T tokens
+            # 2. per-distinct-row sums, then the two GEMMs over U rows instead of T tokens.  After the direct
+            # writes only the segments of two or more tokens are left to sum; with a table gradient to come
+            # that sum is handed to it (its zero fill can ride in the sum's fix-up launch)
             dYu = dYall[T:]
-            absent_only = (ctx.needs_input_grad[0] and PROJ_DGRAD_TAIL_WS and ABSENT_ROWS_ZERO and
-                           ctx.prec == L.GEMM_BF16X6 and 0 <= pad_row < V)
-            # the zero fill of the table gradient's absent rows depends on the distinct-row scan only:
-            # its workgroups run in the segment sum's fix-up launch (single process)
-            zero_in_segsum = SEGSUM_ZERO_FUSED and direct and absent_only and not _multi_rank()
-            if zero_in_segsum:
-                dtable = table_grad_buffer(ctx.table_ref, V, E, table.device, zero=False)
-                rflags = _zero_absent_word_rows(ctx.table_ref, dtable, ur, pad_row, segsum=(dY, dYu))
-            elif direct:
-                ur.segment_sum_multi(dY, dYu)
-            else:
+            if not direct:
                 ur.segment_sum(dY, dYu)
+            elif not ctx.needs_input_grad[0]:
+                ur.segment_sum_multi(dY, dYu)
+            # 3. table gradient
             inflight = False
             if ctx.needs_input_grad[0]:
-                if zero_in_segsum:
-                    pass
-                elif absent_only:
-                    # every present row is stored by the dgrad (its tail through the workspace, no
-                    # atomics): zero only the absent rows and the pad row instead of the whole table
-                    dtable = table_grad_buffer(ctx.table_ref, V, E, table.device, zero=False)
-                    rflags = _zero_absent_word_rows(ctx.table_ref, dtable, ur, pad_row)
-                else:
-                    dtable = table_grad_buffer(ctx.table_ref, V, E, table.device, zero=True)
-                # distinct rows (M = U, not U_pad: no duplicate pad ids): plain row stores
-                wt = K.transpose(w_cat) if PROJ_DGRAD_KC else None   # kept alive by the closure
-
-                def dgrad(dtable=dtable):   # bound now: the hook below may take the name's buffer
-                    w_b = K.operand(wt, L.KCONTIG) if wt is not None else K.operand(w_cat, L.MNCONTIG)
-                    K.gemm_dyn(ur.cap, E, NY, K.operand(dYu, L.KCONTIG), w_b, dtable,
-                               m_dev=ur.n_rows, epilogue=L.EPI_SCATTER_ZEROED,
-                               c_rows=K.rows_map(ur.uids, L.ROWS_GATHER), pad_row=pad_row,
-                               workspace=PROJ_DGRAD_TAIL_WS)
-                PROBE.run("proj_dgrad", dgrad, dtable, ur)
-                if TABLE_GRAD_HOOK(ctx.table_ref, dtable):
-                    dtable = None
-                    inflight = True   # the table's all-reduce runs beside the weight gradient
-                _word_row_flags(ctx.table_ref, dtable, rflags)
+                dtable, inflight = _word_table_grad(ctx.table_ref, dYu, K.operand(w_cat, L.MNCONTIG), ur, pad_row,
+                                                    ctx.prec, bf16_store=False,
+                                                    segsum=(dY, dYu) if direct else None, probe=True)
+            # 4. weight gradient
             prec = ctx.prec
 
             def wgrad(max_cus=0):
                 K.gemm_dyn(NY, E, ur.cap, K.operand(dYu, L.MNCONTIG),
                            K.operand(table, L.MNCONTIG, rows=ur.uids, mapping=L.ROWS_GATHER), dw, k_dev=ur.u_pad,
                            epilogue=L.EPI_ATOMIC, split_k=_split_k(NY, E, ur.cap), prec=prec, max_cus=max_cus,
-                           workspace=PROJ_WGRAD_WS)
+                           workspace=True)
             if not WGRAD_DEFER_HOOK(wgrad, dw):
                 cus = WGRAD_DEFER_HOOK.max_cus if inflight else 0
                 PROBE.run("proj_wgrad", lambda: wgrad(cus), dw, ur)
@@ -797,15 +770,15 @@ class CNNNewsFn(torch.autograd.Function):
 class CNNWeightsFn(torch.autograd.Function):
     """The distinct-row CNN encoder's weight operands (nr_cnn_pack_weights): the Conv1d weight
     [H, E, 3] as w3t [3*Hp, E] (row tap*Hp + h), its transpose w3tt [E, 3*Hp] (the table dgrad's
-    K-contiguous weight, CNN_DGRAD_KC; None otherwise) and the key projection zero-padded to
-    [Hp, Hp] / [Hp], in one launch; the backward maps the three gradients back in one launch."""
+    K-contiguous weight, 1.5 MB per step) and the key projection zero-padded to [Hp, Hp] / [Hp],
+    in one launch; the backward maps the three gradients back in one launch."""
 
     @staticmethod
     def forward(ctx, conv_w, wq, bq, Hp):
         H, E = conv_w.shape[0], conv_w.shape[1]
         dev = conv_w.device
         w3t = torch.empty(3 * Hp, E, device=dev)
-        w3tt = torch.empty(E, 3 * Hp, device=dev) if CNN_DGRAD_KC else None
+        w3tt = torch.empty(E, 3 * Hp, device=dev)
         wqp = torch.empty(Hp, Hp, device=dev)
         bqp = torch.empty(Hp, device=dev)
         for t in (conv_w, wq, bq):
@@ -814,8 +787,7 @@ class CNNWeightsFn(torch.autograd.Function):
         L.call("nr_cnn_pack_weights", L.ptr(conv_w), L.ptr(wq), L.ptr(bq), H, E, Hp, L.ptr(w3t), L.ptr(wqp),
                L.ptr(bqp), L.ptr(w3tt), L.stream_ptr(conv_w))
         ctx.cfg = (H, E, Hp)
-        if w3tt is not None:
-            ctx.mark_non_differentiable(w3tt)
+        ctx.mark_non_differentiable(w3tt)
         return w3t, wqp, bqp, w3tt
 
     @staticmethod
@@ -871,8 +843,8 @@ class CNNNewsRowsFn(_GradAwareFn):
         fused = FUSED_KEYPOOL and K.cnn_keypool_supported(Hp, seq_len)
         if fused:
             # key projection + tanh + pooling per title; with a backward to come K is kept (the backward
-            # reads it instead of recomputing the key products, KEYPOOL_SAVE_K)
-            Kq = _empty(T, Hp, table) if KEYPOOL_SAVE_K and _backward_possible(ctx) else None
+            # reads it instead of recomputing the key products)
+            Kq = _empty(T, Hp, table) if _backward_possible(ctx) else None
             K.cnn_keypool_fwd(C, wq, bq, query, mask, n, seq_len, news, probs, qn=H, prec=ctx.prec, kout=Kq)
         else:
             Kq = _empty(T, Hp, table)
@@ -892,7 +864,6 @@ class CNNNewsRowsFn(_GradAwareFn):
     def backward(ctx, dnews, dC_out):
         table, ids, mask, w3t, wq, bq, query, C, Kq, probs, w3tt = ctx.saved_tensors
         _word_row_flags(ctx.table_ref, None, None)
-        rflags = None
         seq_len, pad_row, H, fused = ctx.cfg
         ur = ctx.ur
         T = ids.numel()
@@ -906,9 +877,10 @@ class CNNNewsRowsFn(_GradAwareFn):
         dwq, dbq, dconv_b, dw3t, dq = _backward_zeros(ctx, dev, (Hp, Hp), (Hp,), (H,), (3 * Hp, E), (H,))
         if dnews.stride(-1) != 1:
             dnews = dnews.contiguous()
+        # 1. pooling / key projection backward -> dC per token
         if fused:
-            # one pass per title: key recomputed, pooling / tanh / key-projection backward, ReLU gate,
-            # dWq / dbq / dq / dconv_b summed over per-workgroup partials
+            # one pass per title: K read back (or recomputed without it), pooling / tanh / key-projection
+            # backward, ReLU gate, dWq / dbq / dq / dconv_b summed over per-workgroup partials
             dz = dC_out if dC_out is None or dC_out.stride(-1) == 1 else dC_out.contiguous()
             K.cnn_keypool_bwd(C, wq, bq, query, n, seq_len, H, probs, dnews, dC, dwq, dbq, dq, dconv_b, dz=dz,
                               prec=ctx.prec, kin=Kq)
@@ -925,40 +897,21 @@ class CNNNewsRowsFn(_GradAwareFn):
             K.gemm(T, Hp, Hp, K.operand(dKq, L.KCONTIG), K.operand(wq, L.MNCONTIG), dC, epilogue=L.EPI_ACCUM_GATE,
                    c_rows=K.aux_operand(C))
             K.colsum(dC, T, H, dconv_b)
+        # 2. per-distinct-row sums of the shifted dC rows
         S = _empty(ur.cap, 3 * Hp, table)
         ur.segment_sum_conv3(dC, S, Hp, seq_len)
+        # 3. table gradient, over the weights transposed by the pack launch so both operands are k-contiguous
         dtable = None
         inflight = False
         if ctx.needs_input_grad[0]:
-            # the dgrad stores every present row -- bf16x6: its stream-K tail through the workspace;
-            # bf16: as plain scatter stores (NR_EPI_SCATTER_STORE: no atomic tail, which would need
-            # zeroed rows) -- so only the absent rows and the pad row are zeroed
-            epi = L.EPI_SCATTER_ZEROED
-            if ABSENT_ROWS_ZERO and 0 <= pad_row < V and ((PROJ_DGRAD_TAIL_WS and ctx.prec == L.GEMM_BF16X6) or
-                                                          ctx.prec == L.GEMM_BF16):
-                if ctx.prec == L.GEMM_BF16:
-                    epi = L.EPI_SCATTER_STORE
-                dtable = table_grad_buffer(ctx.table_ref, V, E, dev, zero=False)
-                rflags = _zero_absent_word_rows(ctx.table_ref, dtable, ur, pad_row)
-            else:
-                dtable = table_grad_buffer(ctx.table_ref, V, E, dev, zero=True)
-            if CNN_DGRAD_KC:   # the weights transposed (1.5 MB, by the pack launch) so both operands are k-contiguous
-                w_b = K.operand(w3tt if w3tt is not None else w3t.t().contiguous(), L.KCONTIG)
-            else:
-                w_b = K.operand(w3t, L.MNCONTIG)
-            K.gemm_dyn(ur.cap, E, 3 * Hp, K.operand(S, L.KCONTIG), w_b, dtable,
-                       m_dev=ur.n_rows, epilogue=epi, c_rows=K.rows_map(ur.uids, L.ROWS_GATHER),
-                       pad_row=pad_row, workspace=PROJ_DGRAD_TAIL_WS)
-            if TABLE_GRAD_HOOK(ctx.table_ref, dtable):
-                dtable = None
-                inflight = True
-            _word_row_flags(ctx.table_ref, dtable, rflags)
+            w_b = K.operand(w3tt if w3tt is not None else w3t.t().contiguous(), L.KCONTIG)
+            dtable, inflight = _word_table_grad(ctx.table_ref, S, w_b, ur, pad_row, ctx.prec, bf16_store=True)
+        # 4. weight gradient (split-K partials through the workspace under bf16 and bf16x6)
         K.gemm_dyn(3 * Hp, E, ur.cap, K.operand(S, L.MNCONTIG),
                    K.operand(table, L.MNCONTIG, rows=ur.uids, mapping=L.ROWS_GATHER), dw3t, k_dev=ur.u_pad,
                    epilogue=L.EPI_ATOMIC, split_k=_split_k(3 * Hp, E, ur.cap),
                    max_cus=WGRAD_DEFER_HOOK.max_cus if inflight else 0,
-                   workspace=(WGRAD_WS_BF16 and ctx.prec == L.GEMM_BF16) or
-                   (WGRAD_WS_BF16X6 and ctx.prec == L.GEMM_BF16X6))
+                   workspace=ctx.prec in (L.GEMM_BF16, L.GEMM_BF16X6))
         return (dtable, None, None, dw3t, dconv_b, dwq, dbq, dq.view_as(query), None, None, None, None)
 
 
@@ -1047,18 +1000,14 @@ class MHAFn(_GradAwareFn):
             dx = torch.zeros(rows, D, device=dev)
             K.gemm(rows, D, NY, K.operand(dY, L.KCONTIG), K.operand(w_cat, L.MNCONTIG), dx, epilogue=L.EPI_ATOMIC,
                    split_k=split)
-        elif USER_GEMM_PAIR:
+            _proj_wgrad(dY, K.operand(x, L.MNCONTIG), dw, None, rows)
+        else:
             # dx = dY W and dW += dYᵀ x read the same dY and depend on nothing else: one launch
             # (_proj_wgrad's GEMM without a bias gradient: db came from the attention backward)
             dx = _grad_out(ctx.dx_dest, rows, D, x)
             K.gemm_pair(K.gemm_desc(rows, D, NY, K.operand(dY, L.KCONTIG), K.operand(w_cat, L.MNCONTIG), dx),
                         K.gemm_desc(NY, D, rows, K.operand(dY, L.MNCONTIG), K.operand(x, L.MNCONTIG), dw,
                                     epilogue=L.EPI_ATOMIC, split_k=_split_k(NY, D, rows)), dx)
-            return dx, None, dw, db, None, None, None, None, None
-        else:
-            dx = _grad_out(ctx.dx_dest, rows, D, x)
-            K.gemm(rows, D, NY, K.operand(dY, L.KCONTIG), K.operand(w_cat, L.MNCONTIG), dx)
-        _proj_wgrad(dY, K.operand(x, L.MNCONTIG), dw, None, rows)
         return dx, None, dw, db, None, None, None, None, None
 
 

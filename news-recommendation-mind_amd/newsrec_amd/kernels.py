@@ -272,18 +272,20 @@ class UniqueRows:
         self.n_rows = self.counts[0:1]  # device scalar: U
         self.u_pad = self.counts[1:2]   # device scalar: U_pad, the GEMM extent
 
-    def segment_sum(self, src, dst):
-        """dst[u] = Σ src[t] over the tokens t of distinct row u (zeros on pad rows)."""
+    def _segment_sum(self, entry, src, dst):
         _f32(src, dst)
         _rows_ok(src, self.T, src.shape[1], "segment_sum src")
         _rows_ok(dst, self.cap, src.shape[1], "segment_sum dst")
         width = src.shape[1]
         nbytes = L.load().nr_segment_rows_sum_workspace(self.T, width)
         work = torch.empty(max(1, nbytes // 4), device=src.device, dtype=torch.float32)
-        L.call("nr_segment_rows_sum", L.ptr(src), src.stride(0), width, self.T, L.ptr(self.seg_off),
+        L.call(entry, L.ptr(src), src.stride(0), width, self.T, L.ptr(self.seg_off),
                L.ptr(self.seg_tok), L.ptr(self.seg_of), L.ptr(self.counts), self.cap, L.ptr(work), L.ptr(dst),
                dst.stride(0), L.stream_ptr(src))
 
+    def segment_sum(self, src, dst):
+        """dst[u] = Σ src[t] over the tokens t of distinct row u (zeros on pad rows)."""
+        self._segment_sum("nr_segment_rows_sum", src, dst)
 
     def zero_absent_rows(self, dst, pad_row, flags=None):
         """Zero the rows of dst [vocab, W] whose id is absent from this batch, and the pad row (the
@@ -308,15 +310,7 @@ class UniqueRows:
     def segment_sum_multi(self, src, dst):
         """segment_sum for the distinct rows of two or more CSR tokens; a one-token row of dst is left
         as it is (its producer wrote it: mha_pool_bwd with seg=)."""
-        _f32(src, dst)
-        _rows_ok(src, self.T, src.shape[1], "segment_sum src")
-        _rows_ok(dst, self.cap, src.shape[1], "segment_sum dst")
-        width = src.shape[1]
-        nbytes = L.load().nr_segment_rows_sum_workspace(self.T, width)
-        work = torch.empty(max(1, nbytes // 4), device=src.device, dtype=torch.float32)
-        L.call("nr_segment_rows_sum_multi", L.ptr(src), src.stride(0), width, self.T, L.ptr(self.seg_off),
-               L.ptr(self.seg_tok), L.ptr(self.seg_of), L.ptr(self.counts), self.cap, L.ptr(work), L.ptr(dst),
-               dst.stride(0), L.stream_ptr(src))
+        self._segment_sum("nr_segment_rows_sum_multi", src, dst)
 
     def segment_sum_multi_zero(self, src, dst, zdst, pad_row, flags=None):
         """``segment_sum_multi(src, dst)`` and ``zero_absent_rows(zdst, pad_row, flags)`` with the zero

@@ -60,7 +60,7 @@ def _ref(pre, wq, bq, q, mask, dnews, dz):
 @pytest.mark.parametrize("save_k", [False, True])
 def test_cnn_keypool_matches_float64(prec, tol, nseq, L_, H, with_dz, save_k):
     """save_k: the forward stores K = tanh(C wqᵀ + bq) (checked here too) and the backward reads it
-    instead of recomputing the key products (functions.KEYPOOL_SAVE_K)."""
+    instead of recomputing the key products (the form functions.CNNNewsRowsFn trains with)."""
     Hp = (H + 31) // 32 * 32
     dev = "cuda"
     pre, wq, bq, q, mask, dnews, dz = _case(nseq, L_, H, Hp, nseq + H + L_, with_dz)

@@ -1,6 +1,7 @@
 """A/B of the NRMS train step (bench.py's headline, graphed, device-formed batches) under module-level
 switches (newsrec_amd.functions NAME, or encoders.NAME / bench.NAME), interleaved in ONE process (rounds x variants), so box-to-box and
-clock drift cancel.  python tools/ab_step.py DEDUP_ROWS=1 DEDUP_ROWS=0 [--rounds 3 --steps 20]"""
+clock drift cancel.  python tools/ab_step.py DEDUP_ROWS=1 DEDUP_ROWS=0 [--rounds 3 --steps 20]
+functions keeps DEDUP_ROWS, USER_DGRAD_SPLIT and FUSED_KEYPOOL; the settled A/Bs are a table in DESIGN.md (§4.4)."""
 import argparse
 import json
 import os
