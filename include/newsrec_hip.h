@@ -475,7 +475,10 @@ enum nr_score_mode { NR_SCORE_RAW = 0, NR_SCORE_LOG_SOFTMAX = 1, NR_SCORE_SIGMOI
 
 /* logits[b][c] = head(cdd_row(b,c) · user[b] / sqrt(H)); cdd_row = cdd[cdd_idx[b*C+c]]
  * (predict_fast's news-table gather, TwoTowerBaseModel.py:80) or cdd[b*C+c].
- * Replaces compute_score + log_softmax / sigmoid (TwoTowerBaseModel.py:51-75). */
+ * Replaces compute_score + log_softmax / sigmoid (TwoTowerBaseModel.py:51-75).
+ * One workgroup per impression keeps its C scores in C * 4 bytes of dynamic LDS: C <= 16 * 1024.
+ * Errors (before any HIP call): -1000 B < 0, C < 1, C > 16 * 1024, H < 1 or a mode outside the enum;
+ * -1001 cdd, user or logits NULL.  B == 0 returns 0 without a launch. */
 int nr_score_fwd(const float* cdd, int64_t ldc, const int64_t* cdd_idx, const float* user,
                  int64_t ldu, int64_t B, int32_t C, int32_t H, int32_t mode, float* logits,
                  hipStream_t stream);
@@ -490,7 +493,10 @@ int nr_score_fwd(const float* cdd, int64_t ldc, const int64_t* cdd_idx, const fl
  * status the caller reads and clears itself.  work: nr_score_nll_workspace(B) int32,
  * all zero before the first call; every call leaves work[0] zero again (work[1] is the status, the
  * rest scratch), so one buffer serves every call on a stream.  Calls on one buffer must not run
- * concurrently. */
+ * concurrently.
+ * Errors (before any HIP call): -1000 B < 1 (the mean over no impression: there is no empty case),
+ * B > 2^31 - 1, C < 1, C > 16 * 1024 (the C scores sit in C * 4 bytes of dynamic LDS) or H < 1;
+ * -1001 cdd, user, label, logits, loss or work NULL. */
 int nr_score_nll_fwd(const float* cdd, int64_t ldc, const float* user, int64_t ldu,
                      const int64_t* label, int64_t B, int32_t C, int32_t H, float* logits, float* loss,
                      int32_t* work, hipStream_t stream);
@@ -499,13 +505,19 @@ int64_t nr_score_nll_workspace(int64_t B);
 
 /* Backward of nr_score_nll_fwd: the gradient of the loss (dloss, a device scalar, or NULL; spread
  * over the labels in [0, C) as 1/count each) plus an optional gradient of the logits themselves
- * (dlogits [B][C] or NULL). */
+ * (dlogits [B][C] or NULL).
+ * Errors (before any HIP call): -1000 B < 0, C < 1, C > 16 * 1024 (dynamic LDS, as the forward) or
+ * H < 1; -1001 cdd, user, logits, label, dcdd or duser NULL.  B == 0 returns 0 without a launch. */
 int nr_score_nll_bwd(const float* cdd, int64_t ldc, const float* user, int64_t ldu,
                      const float* logits, const int64_t* label, const float* dloss,
                      const float* dlogits, int64_t B, int32_t C, int32_t H, float* dcdd, int64_t lddc,
                      float* duser, int64_t lddu, hipStream_t stream);
 
-/* Backward of nr_score_fwd (cdd_idx == NULL form) given dlogits [B][C]. */
+/* Backward of nr_score_fwd (cdd_idx == NULL form) given dlogits [B][C]; logits is the forward's
+ * output (read by the log-softmax and sigmoid heads).
+ * Errors (before any HIP call): -1000 B < 0, C < 1, C > 16 * 1024 (dynamic LDS, as the forward),
+ * H < 1 or a mode outside the enum; -1001 cdd, user, logits, dlogits, dcdd or duser NULL.  B == 0
+ * returns 0 without a launch. */
 int nr_score_bwd(const float* cdd, int64_t ldc, const float* user, int64_t ldu,
                  const float* logits, const float* dlogits, int64_t B, int32_t C, int32_t H,
                  int32_t mode, float* dcdd, int64_t lddc, float* duser, int64_t lddu,
@@ -515,7 +527,10 @@ int nr_score_bwd(const float* cdd, int64_t ldc, const float* user, int64_t ldu,
  * 1-based step count after increment (bias corrections as torch).  The gradient is read as
  * grad * grad_scale (1/world_size folds the data-parallel mean into the update).  step_dev
  * (optional): the step count read on the device instead (graph replays).
- * Manager.py:404-413,647. */
+ * Manager.py:404-413,647.
+ * Errors (before any HIP call), in this order: -1000 n < 0, or step < 1 without step_dev; -1001
+ * param, grad, exp_avg or exp_avg_sq NULL; -1002 one of the four not on a 16-byte boundary (float4
+ * accesses).  n == 0 then returns 0 without a launch. */
 int nr_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
             float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
             const int64_t* step_dev, float grad_scale, hipStream_t stream);
@@ -602,12 +617,16 @@ int nr_adam_multi_clip(const nr_adam_tensor* tensors, int32_t count, float beta1
                        float weight_decay, const nr_clip_state* clip, int32_t honor_skip,
                        int32_t* ticket, hipStream_t stream);
 
-/* out[i] = table[idx[i]] rows of E floats (E % 4 == 0).  BERT_Embedding.forward, BERT.py:39. */
+/* out[i] = table[idx[i]] rows of E floats (E % 4 == 0).  BERT_Embedding.forward, BERT.py:39.
+ * Errors (before any HIP call): -1000 V < 1, E < 4, E % 4 != 0 or n < 0; -1001 table, idx or out
+ * NULL.  n == 0 returns 0 without a launch. */
 int nr_embedding_fwd(const float* table, int64_t V, int64_t E, const int64_t* idx, int64_t n,
                      float* out, hipStream_t stream);
 
 /* dtable[idx[i]] += dout[i] for idx[i] != padding_idx (atomic; dtable pre-zeroed):
- * embedding_dense_backward with nn.Embedding(padding_idx=0). */
+ * embedding_dense_backward with nn.Embedding(padding_idx=0).
+ * Errors (before any HIP call): -1000 V < 1, E < 1 or n < 0; -1001 dout, idx or dtable NULL.
+ * n == 0 returns 0 without a launch. */
 int nr_embedding_bwd(const float* dout, int64_t V, int64_t E, const int64_t* idx, int64_t n,
                      int64_t padding_idx, float* dtable, hipStream_t stream);
 
@@ -616,27 +635,38 @@ int nr_embedding_bwd(const float* dout, int64_t V, int64_t E, const int64_t* idx
  * ids (no atomics).  For row-sparse gradients of few rows (n <= 2^20; O(n^2) id reads): LSTUR's user
  * table (embedding_dense_backward of userEmbedding, models/Encoders/RNN.py:100-104) on one process and
  * in the data-parallel row-sparse exchange (the DDP mean of twotower.py:49-50), so every rank forms
- * the same bits. */
+ * the same bits.  Ids outside [0, V) are dropped.
+ * Errors (before any HIP call): -1000 V < 1, E < 1, n < 0, n > 2^20, ldo < E or ldt < E; -1001 dout,
+ * idx or dtable NULL.  n == 0 returns 0 without a launch. */
 int nr_rows_add_ordered(const float* dout, int64_t ldo, int64_t V, int64_t E, const int64_t* idx, int64_t n,
                         int64_t padding_idx, float* dtable, int64_t ldt, hipStream_t stream);
 
 /* XSoftmax (models/Modules/Attention.py:56-80) over the last dimension: out = softmax of x's rows
  * with the entries whose mask (same [rows, cols] shape, enum nr_mask_dtype) is zero excluded, those
  * entries exactly 0, a fully masked row all 0.  Backward (_softmax_backward_data, Attention.py:77-80):
- * dx = y (dy - Σ_row dy y).  Contiguous [rows, cols] tensors, one wave per row. */
+ * dx = y (dy - Σ_row dy y).  Contiguous [rows, cols] tensors, one wave per row.  A masked entry of x
+ * is never read as a number: it may hold NaN or inf.
+ * Errors (before any HIP call): -1000 rows < 0, cols < 0 or (forward) a mask_dtype outside the enum;
+ * -1001 a NULL pointer (x, mask, out; y, dy, dx).  rows == 0 or cols == 0 returns 0 without a launch. */
 int nr_xsoftmax_fwd(const float* x, const void* mask, int32_t mask_dtype, int64_t rows, int64_t cols,
                     float* out, hipStream_t stream);
 int nr_xsoftmax_bwd(const float* y, const float* dy, int64_t rows, int64_t cols, float* dx, hipStream_t stream);
 
 /* dst[i][:] = src[idx[i]][:] for rows of `cols` floats (any width; leading dimensions lds / ldd): the
  * news-table rows of the fast-eval history slots (predict_fast's encode_user over the cached table,
- * TwoTowerBaseModel.py:78-83 / Manager.py:516). */
+ * TwoTowerBaseModel.py:78-83 / Manager.py:516).  Rows move as float4 when cols, lds and ldd are
+ * multiples of 4 and src and dst are 16-byte aligned, else float by float.  src has V rows; the
+ * ids are not range-checked.
+ * Errors (before any HIP call): -1000 n < 0, cols < 0, V < 1, lds < cols or ldd < cols; -1001 src,
+ * idx or dst NULL.  n == 0 or cols == 0 returns 0 without a launch. */
 int nr_gather_rows_f32(const float* src, int64_t lds, int64_t V, const int64_t* idx, int64_t n, int64_t cols,
                        float* dst, int64_t ldd, hipStream_t stream);
 
 /* dst[c][r] = src[r][c] for a [rows, cols] fp32 matrix (leading dimensions lds >= cols, ldd >= rows):
  * the NRMS table-gradient GEMM's k-contiguous copy of the joint [keyProject; valueProject] weight
- * (models/Modules/Attention.py:107-108), so both of its operands take the K-contiguous loaders. */
+ * (models/Modules/Attention.py:107-108), so both of its operands take the K-contiguous loaders.
+ * Errors (before any HIP call): -1000 rows < 0, cols < 0, lds < cols, ldd < rows, rows > 65535 * 64
+ * or cols > 2^31 (the grid); -1001 src or dst NULL.  rows == 0 or cols == 0 returns 0 without a launch. */
 int nr_transpose_f32(const float* src, int64_t lds, int64_t rows, int64_t cols, float* dst, int64_t ldd,
                      hipStream_t stream);
 
@@ -647,7 +677,10 @@ int nr_colsum(const float* x, int64_t ldx, int64_t rows, int64_t cols, float* ou
               hipStream_t stream);
 /* nr_colsum in one launch: the last workgroup to finish each 64-column chunk sums that chunk's
  * partial rows (fixed order: the same result as nr_colsum).  tick: ceil(cols / 64) int32 arrival
- * counters, zero before the first call and left zero by every call. */
+ * counters, zero before the first call and left zero by every call.
+ * Errors of both (before any HIP call): -1000 rows < 0, cols < 0 or ldx < cols; -1001 x or out NULL,
+ * or work (nr_colsum_ws: work or tick) NULL with rows > 0 and cols > 0.  rows == 0 or cols == 0
+ * returns 0 without a launch (out is left as it is). */
 int nr_colsum_ws(const float* x, int64_t ldx, int64_t rows, int64_t cols, float* out, float* work,
                  int32_t* tick, hipStream_t stream);
 

@@ -797,10 +797,14 @@ void colsum_grid(int64_t rows, int64_t cols, int64_t* nrb, int64_t* rb_rows, int
 
 }  // namespace
 
+// the scorer kernels keep the C scores of an impression in dynamic LDS (C * 4 bytes): 64 KB at most,
+// what a launch gets without raising the function's limit
+constexpr int32_t kScoreMaxC = 16 * 1024;
+
 extern "C" int nr_score_fwd(const float* cdd, int64_t ldc, const int64_t* cdd_idx, const float* user,
                             int64_t ldu, int64_t B, int32_t C, int32_t H, int32_t mode, float* logits,
                             hipStream_t stream) {
-  if (B < 0 || C < 1 || H < 1 || mode < 0 || mode > 2) return NR_EINVAL(0);
+  if (B < 0 || C < 1 || C > kScoreMaxC || H < 1 || mode < 0 || mode > 2) return NR_EINVAL(0);
   if (!cdd || !user || !logits) return NR_EINVAL(1);
   if (B == 0) return NR_OK;
   hipLaunchKernelGGL(score_fwd_kernel, dim3((unsigned)B), dim3(256), (size_t)C * sizeof(float), stream, cdd,
@@ -813,7 +817,7 @@ extern "C" int nr_score_bwd(const float* cdd, int64_t ldc, const float* user, in
                             const float* logits, const float* dlogits, int64_t B, int32_t C, int32_t H,
                             int32_t mode, float* dcdd, int64_t lddc, float* duser, int64_t lddu,
                             hipStream_t stream) {
-  if (B < 0 || C < 1 || H < 1 || mode < 0 || mode > 2) return NR_EINVAL(0);
+  if (B < 0 || C < 1 || C > kScoreMaxC || H < 1 || mode < 0 || mode > 2) return NR_EINVAL(0);
   if (!cdd || !user || !logits || !dlogits || !dcdd || !duser) return NR_EINVAL(1);
   if (B == 0) return NR_OK;
   hipLaunchKernelGGL(score_bwd_kernel, dim3((unsigned)B), dim3(256), (size_t)C * sizeof(float), stream, cdd,
@@ -826,7 +830,7 @@ extern "C" int nr_score_bwd(const float* cdd, int64_t ldc, const float* user, in
 extern "C" int nr_score_nll_fwd(const float* cdd, int64_t ldc, const float* user, int64_t ldu,
                                 const int64_t* label, int64_t B, int32_t C, int32_t H, float* logits, float* loss,
                                 int32_t* work, hipStream_t stream) {
-  if (B < 1 || B > 0x7fffffff || C < 1 || C > 16 * 1024 || H < 1) return NR_EINVAL(0);
+  if (B < 1 || B > 0x7fffffff || C < 1 || C > kScoreMaxC || H < 1) return NR_EINVAL(0);
   if (!cdd || !user || !label || !logits || !loss || !work) return NR_EINVAL(1);
   const int waves = C < 16 ? C : 16;
   hipLaunchKernelGGL(score_nll_fwd_kernel, dim3((unsigned)B), dim3(64 * waves), (size_t)C * sizeof(float), stream,
@@ -841,7 +845,7 @@ extern "C" int nr_score_nll_bwd(const float* cdd, int64_t ldc, const float* user
                                 const float* logits, const int64_t* label, const float* dloss,
                                 const float* dlogits, int64_t B, int32_t C, int32_t H, float* dcdd, int64_t lddc,
                                 float* duser, int64_t lddu, hipStream_t stream) {
-  if (B < 0 || C < 1 || H < 1) return NR_EINVAL(0);
+  if (B < 0 || C < 1 || C > kScoreMaxC || H < 1) return NR_EINVAL(0);
   if (!cdd || !user || !logits || !label || !dcdd || !duser) return NR_EINVAL(1);
   if (B == 0) return NR_OK;
   hipLaunchKernelGGL(score_nll_bwd_kernel, dim3((unsigned)B), dim3(256), (size_t)C * sizeof(float), stream, cdd,

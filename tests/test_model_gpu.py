@@ -90,7 +90,8 @@ def test_fused_adam_parity():
 
 
 def test_fused_adam_kernel_matches_torch_adam():
-    """nr_adam against torch.optim.Adam on identical gradients (no model noise)."""
+    """FusedAdam, hence nr_adam_multi, against torch.optim.Adam on identical gradients (no model noise).
+    The single-tensor entry nr_adam is held to float64 by test_score_kernels_gpu.test_adam_single_tensor."""
     from newsrec_amd.optim import FusedAdam
     g = torch.Generator().manual_seed(0)
     shapes = [(1000, 77), (3,), (4097,)]

@@ -48,14 +48,21 @@ def expected(table, user, k, first_row=1, row_mask=None, exclude=None):
     return ids, sc
 
 
+def dot_tolerance(absdot, dot, H):
+    """Bound on |fp32 score - float64 score| of one H-term dot product given sum_k |u_k t_k| and
+    sum_k u_k t_k in float64: the gamma_H bound of an H-term fp32 fma chain, 2 H 2^-24 sum_k |u_k t_k|,
+    plus the rounding of the scale multiply, 2^-23 |s|, times the scale.  (Shared with
+    score_util.score_tolerance, the scorer kernels' bound.)"""
+    return (2.0 * H * 2.0 ** -24 * absdot + 2.0 ** -23 * np.abs(dot)) * np.float64(scale32(H))
+
+
 def tolerances(table, user):
-    """[U, N] bound on |fp32 score - float64 score|: the gamma_H bound of an H-term fp32 fma chain,
-    2 H 2^-24 sum_k |u_k t_k|, plus the rounding of the scale multiply, 2^-23 |s|, times the scale."""
+    """[U, N] dot_tolerance of every (user, table row) pair."""
     H = table.shape[1]
     t64, u64 = table.astype(np.float64), user.astype(np.float64)
     absdot = np.abs(u64) @ np.abs(t64).T
     dot = u64 @ t64.T
-    return (2.0 * H * 2.0 ** -24 * absdot + 2.0 ** -23 * np.abs(dot)) * np.float64(scale32(H))
+    return dot_tolerance(absdot, dot, H)
 
 
 def check_properties(table, user, ids, scores, k, first_row=1, row_mask=None, exclude=None):
