@@ -56,8 +56,18 @@ typedef struct nr_operand {
   int32_t layout;      /* enum nr_layout                                                   */
 } nr_operand;
 
+/* What a GEMM does with its accumulators.  `bias` ([N], may be NULL = zeros) is READ by NR_EPI_STORE,
+ * _STORE_RELU, _STORE_TANH, _ACCUM and _STORE_GELU only; every other epilogue (_ATOMIC, _SCATTER*,
+ * _ACCUM_GATE, _GELU_GRAD) ignores it -- its values never reach C, whatever they are (its alignment
+ * may still cost the float4 stores: only a 16-B aligned or NULL bias keeps them).  `aux` (the matrix
+ * of _ACCUM_GATE, _STORE_GELU and _GELU_GRAD, passed as c_rows->data) is addressed as
+ * aux[m * c_rows->ld + n] with ITS OWN ld, independent of ldc; _ACCUM_GATE and _GELU_GRAD only read
+ * it, _STORE_GELU writes its [M][N] window.  With a device-resident M, rows at and past *m_dev of C
+ * and of aux are neither read nor written.  Any ldc / aux ld >= N and any 4-B aligned C, bias and
+ * aux are valid; float4 accesses are used when N, ldc (and the aux ld) are multiples of 4 and C,
+ * bias (and aux) are 16-B aligned, scalar ones otherwise, with the same arithmetic. */
 enum nr_epilogue {
-  NR_EPI_STORE = 0,      /* C[m][n] = acc + bias[n]                                          */
+  NR_EPI_STORE = 0,     /* C[m][n] = acc + bias[n]                                          */
   NR_EPI_STORE_RELU = 1, /* C[m][n] = max(acc + bias[n], 0)                 (CNN.py:41-42)   */
   NR_EPI_ATOMIC = 2,     /* C[m][n] += acc  (split-K weight gradients; C pre-zeroed)          */
   NR_EPI_SCATTER = 3,    /* C[c_rows(m)][n'] += acc, rows equal to pad_row skipped: the

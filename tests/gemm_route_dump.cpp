@@ -1,7 +1,10 @@
 // Prints the GEMM route (csrc/gemm_route.h) of a table of problems on a 256-CU device, one line per
 // problem.  Stand-alone and HIP-free: tests/test_gemm_route_cpu.py builds it with g++ (address and
 // undefined-behaviour sanitizers on), runs it and compares the lines with the recorded table.
+// With arguments it prints the route of the one problem they describe (dump_argv below):
+// tests/test_gemm_epi_ref_cpu.py pins the kernels of the epilogue tests' case table that way.
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../news-recommendation-mind_amd/csrc/gemm_route.h"
@@ -154,9 +157,49 @@ const Row ROWS_TABLE[] = {
     {"splitk_scatter", 8000, E, 2304, kc(2304), mn(E), NR_EPI_SCATTER, 4, STATIC, 0, 0, false},
 };
 
+// Argument mode: the route of one problem of plain operands,
+//   NAME M N K A_LAYOUT A_LD B_LAYOUT B_LD EPILOGUE FORM PREC
+// with layouts kc | mn, the epilogue's number (enum nr_epilogue), FORM static | dyn | mdev and PREC
+// f32 | bf16x6 | bf16; one line in the table's format.  Anything else: usage on stderr, exit 2.
+int pick(const char* s, const char* const* names, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!strcmp(s, names[i])) return i;
+  return -1;
+}
+
+bool number(const char* s, int64_t lo, int64_t hi, int64_t& v) {
+  char* end = nullptr;
+  const long long x = strtoll(s, &end, 10);
+  if (end == s || *end || x < lo || x > hi) return false;
+  v = x;
+  return true;
+}
+
+int dump_argv(char** a) {
+  static const char* const layouts[] = {"kc", "mn"};
+  static const char* const forms[] = {"static", "dyn", "mdev"};
+  static const char* const precs[] = {"f32", "bf16x6", "bf16"};
+  int64_t M, N, K, lda, ldb, epi;
+  const int la = pick(a[4], layouts, 2), lb = pick(a[6], layouts, 2), form = pick(a[9], forms, 3);
+  const int prec = pick(a[10], precs, 3);
+  const int64_t big = int64_t(1) << 40;
+  if (!number(a[1], 1, big, M) || !number(a[2], 1, big, N) || !number(a[3], 0, big, K) || la < 0 ||
+      !number(a[5], 1, big, lda) || lb < 0 || !number(a[7], 1, big, ldb) ||
+      !number(a[8], NR_EPI_STORE, NR_EPI_SCATTER_ZEROED, epi) || form < 0 || prec < 0)
+    return 2;
+  const Row w{a[0], M, N, K, Side{la, PLAIN, lda, 1, 0}, Side{lb, PLAIN, ldb, 1, 0}, (int)epi, 1, form, 0, 0, false};
+  dump(w, prec, precs[prec]);   // enum nr_gemm_precision follows the order of precs
+  return 0;
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1) {
+    const int rc = argc == 12 ? dump_argv(argv + 1) : 2;
+    if (rc) fprintf(stderr, "usage: %s [NAME M N K kc|mn A_LD kc|mn B_LD EPILOGUE static|dyn|mdev f32|bf16x6|bf16]\n", argv[0]);
+    return rc;
+  }
   for (const Row& w : ROWS_TABLE) {
     dump(w, NR_GEMM_BF16X6, "bf16x6");
     dump(w, NR_GEMM_BF16, "bf16");

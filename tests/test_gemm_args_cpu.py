@@ -78,6 +78,8 @@ STATIC = [
     ("gathered A, ld=30", dict(A=_op(mapping=L.ROWS_GATHER, ld=30)), -1002),
     ("EPI_SCATTER without c_rows", dict(epilogue=L.EPI_SCATTER), -1004),
     ("EPI_STORE_GELU without aux", dict(epilogue=L.EPI_STORE_GELU), -1004),
+    ("EPI_ACCUM_GATE without aux", dict(epilogue=L.EPI_ACCUM_GATE), -1004),
+    ("EPI_GELU_GRAD without aux", dict(epilogue=L.EPI_GELU_GRAD), -1004),
     ("EPI_SCATTER_STORE without c_rows", dict(epilogue=L.EPI_SCATTER_STORE), -1004),
     ("split_k=2 with EPI_STORE", dict(split_k=2), -1005),
     ("M=0", dict(M=0), 0),

@@ -38,13 +38,16 @@ def _with(base, **kw):
 def _cases(base, bad=(), null=(), ok=()):
     """[(id, args dict, expected code)]: each entry of ``bad`` / ``ok`` is a dict of overrides, each
     name in ``null`` a pointer argument set to NULL."""
+    def label(kw):   # the buffer's address changes from run to run: a test id names it "P"
+        return ", ".join("%s=%s" % (k, "P" if v is P else v) for k, v in kw.items())
+
     out = []
     for kw in bad:
-        out.append((", ".join("%s=%s" % i for i in kw.items()), _with(base, **kw), BAD))
+        out.append((label(kw), _with(base, **kw), BAD))
     for name in null:
         out.append((name + "=NULL", _with(base, **{name: None}), NULL))
     for kw in ok:
-        out.append((", ".join("%s=%s" % i for i in kw.items()) + " -> OK", _with(base, **kw), OK))
+        out.append((label(kw) + " -> OK", _with(base, **kw), OK))
     return out
 
 
