@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(Args g) {
           g.C[row * g.ldc + col] = v * nr_gelu_grad(g.Cm.base[row * g.Cm.ld + col]);
         } else if (g.epi == NR_EPI_ATOMIC) {
           atomicAdd(&g.C[row * g.ldc + col], v);
-        } else {  // NR_EPI_SCATTER
+        } else {  // NR_EPI_SCATTER, NR_EPI_SCATTER_STORE (GATHER rows only: gemm_prepare)
           int64_t tok;
           if (g.Cm.map == NR_ROWS_GATHER) {
             tok = g.Cm.idx[row];
@@ -259,7 +259,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(Args g) {
             tok = row;
           }
           if (tok == g.pad_row) continue;
-          atomicAdd(&g.C[tok * g.ldc + scol], v);
+          if (g.epi == NR_EPI_SCATTER_STORE) {
+            g.C[tok * g.ldc + scol] = v;   // distinct rows, one split: this workgroup owns the element
+          } else {
+            atomicAdd(&g.C[tok * g.ldc + scol], v);
+          }
         }
       }
     }
@@ -294,7 +298,8 @@ int launch_kc(const Args& g, int ak, int bk, int splits, hipStream_t s) {
   return launch<BM, BN, false, false>(g, splits, s);
 }
 
-// the generic kernel: any alignment, the scatter-store epilogues as the same sums via atomics
+// the generic kernel: any alignment; NR_EPI_SCATTER_STORE as plain stores, NR_EPI_SCATTER_ZEROED (rows
+// zero on entry) as the same sums via NR_EPI_SCATTER's atomics (gemm_route)
 int launch_generic(const GemmCall& c, const nrfast::GemmRoute& r) {
   const nrfast::GemmProblem& p = c.p;
   Args g;

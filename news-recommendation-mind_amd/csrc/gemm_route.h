@@ -232,10 +232,11 @@ inline GemmRoute gemm_route(const GemmProblem& p, int cus) {
   if (fast_route(p, t, cus, r)) return r;
   r = GemmRoute();
   if (p.dyn) return r;   // einval 7: not eligible for the fast kernels
-  // generic kernel: any alignment; the scatter-store epilogues as the same sums via atomics
+  // generic kernel: any alignment.  NR_EPI_SCATTER_STORE stores (split_k > 1 is refused for it, so one
+  // workgroup produces each element); NR_EPI_SCATTER_ZEROED, whose rows are zero on entry, runs as the
+  // same sums via NR_EPI_SCATTER's atomics
   const nr_operand *A = p.A, *B = p.B;
-  const bool stores = p.epilogue == NR_EPI_SCATTER_STORE || p.epilogue == NR_EPI_SCATTER_ZEROED;
-  r.epi = stores ? (int)NR_EPI_SCATTER : p.epilogue;
+  r.epi = p.epilogue == NR_EPI_SCATTER_ZEROED ? (int)NR_EPI_SCATTER : p.epilogue;
   r.am = operand_mode(A); r.bmode = operand_mode(B);
   r.splits = ks.splits; r.kchunk = ks.kchunk;
   int bm = pick_tile(p.M), bn = pick_tile(p.N);

@@ -2,7 +2,8 @@
 // problem.  Stand-alone and HIP-free: tests/test_gemm_route_cpu.py builds it with g++ (address and
 // undefined-behaviour sanitizers on), runs it and compares the lines with the recorded table.
 // With arguments it prints the route of the one problem they describe (dump_argv below):
-// tests/test_gemm_epi_ref_cpu.py pins the kernels of the epilogue tests' case table that way.
+// tests/test_gemm_epi_ref_cpu.py and tests/test_gemm_map_ref_cpu.py pin the kernels of the epilogue
+// and row-map tests' case tables that way.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -36,15 +37,17 @@ struct Row {
   int epi, split_k, form, max_cus;
   int work;   // workspace: 0 none, 1 nr_gemm_splitk_workspace(), 2 too small for a round of tail tiles
   bool colsum;
+  int cmap = GATHER, cseg = 1;   // the scatter epilogues' destination row map
+  int seq = 30;                  // tokens per title of every CONV3 map
 };
 
-nr_operand operand(const Side& s) {
+nr_operand operand(const Side& s, int seq) {
   nr_operand o;
   o.data = reinterpret_cast<const float*>(reinterpret_cast<const char*>(DATA) + s.misalign);
   o.ld = s.ld;
   o.rows = s.map == PLAIN ? nullptr : ROWS;
   o.map = s.map;
-  o.seq_len = s.map == CONV3 ? 30 : 1;
+  o.seq_len = s.map == CONV3 ? seq : 1;
   o.seg = s.seg;
   o.layout = s.layout;
   return o;
@@ -56,9 +59,9 @@ const char* family_name(int f) {
 }
 
 void dump(const Row& w, int prec, const char* prec_name) {
-  const nr_operand a = operand(w.A), b = operand(w.B);
+  const nr_operand a = operand(w.A, w.seq), b = operand(w.B, w.seq);
   // c_rows: the destination row map of the scatter epilogues, the aux matrix of the GELU ones
-  const nr_operand rows = operand(Side{KC, GATHER, w.N, 1, 0}), aux = operand(Side{KC, PLAIN, w.N, 1, 0});
+  const nr_operand rows = operand(Side{KC, w.cmap, w.N, w.cseg, 0}, w.seq), aux = operand(Side{KC, PLAIN, w.N, 1, 0}, w.seq);
   const bool scatter = w.epi == NR_EPI_SCATTER || w.epi == NR_EPI_SCATTER_STORE || w.epi == NR_EPI_SCATTER_ZEROED;
   const bool gelu = w.epi == NR_EPI_STORE_GELU || w.epi == NR_EPI_GELU_GRAD;
   GemmProblem p{w.M, w.N, w.K, &a, &b, scatter ? &rows : gelu ? &aux : nullptr, w.epi, w.split_k, prec, w.form != STATIC,
@@ -157,10 +160,14 @@ const Row ROWS_TABLE[] = {
     {"splitk_scatter", 8000, E, 2304, kc(2304), mn(E), NR_EPI_SCATTER, 4, STATIC, 0, 0, false},
 };
 
-// Argument mode: the route of one problem of plain operands,
-//   NAME M N K A_LAYOUT A_LD B_LAYOUT B_LD EPILOGUE FORM PREC
+// Argument mode: the route of one problem,
+//   NAME M N K A_LAYOUT A_LD B_LAYOUT B_LD EPILOGUE FORM PREC [KEY=VALUE ...]
 // with layouts kc | mn, the epilogue's number (enum nr_epilogue), FORM static | dyn | mdev and PREC
-// f32 | bf16x6 | bf16; one line in the table's format.  Anything else: usage on stderr, exit 2.
+// f32 | bf16x6 | bf16; one line in the table's format.  Without KEY=VALUE tokens the operands are plain,
+// split_k is 1 and there is no workspace.  The keys: amap / bmap = plain | gather | conv3 (the operands'
+// row maps) with aseg / bseg (CONV3: columns per tap); cmap = gather | conv3 with cseg (the scatter
+// epilogues' destination map); seq (tokens per title of every CONV3 map, default 30); split (split_k);
+// work = 0 | 1 (nr_gemm_splitk_workspace() floats of workspace).  Anything else: usage on stderr, exit 2.
 int pick(const char* s, const char* const* names, int n) {
   for (int i = 0; i < n; ++i)
     if (!strcmp(s, names[i])) return i;
@@ -175,7 +182,32 @@ bool number(const char* s, int64_t lo, int64_t hi, int64_t& v) {
   return true;
 }
 
-int dump_argv(char** a) {
+// KEY=VALUE tokens of the argument mode into the row; false for an unknown key or a bad value
+bool key_values(char** kv, int n, Row& w) {
+  static const char* const maps[] = {"plain", "gather", "conv3"};   // enum nr_rows_map follows this order
+  for (int i = 0; i < n; ++i) {
+    const char* eq = strchr(kv[i], '=');
+    if (!eq || eq == kv[i]) return false;
+    const size_t kl = (size_t)(eq - kv[i]);
+    const char* val = eq + 1;
+    auto is = [&](const char* k) { return strlen(k) == kl && !strncmp(kv[i], k, kl); };
+    int64_t v = 0;
+    const int m = pick(val, maps, 3);
+    if (is("amap") && m >= 0) w.A.map = m;
+    else if (is("bmap") && m >= 0) w.B.map = m;
+    else if (is("cmap") && m >= 1) w.cmap = m;
+    else if (is("aseg") && number(val, 1, 1 << 30, v)) w.A.seg = (int)v;
+    else if (is("bseg") && number(val, 1, 1 << 30, v)) w.B.seg = (int)v;
+    else if (is("cseg") && number(val, 1, 1 << 30, v)) w.cseg = (int)v;
+    else if (is("seq") && number(val, 1, 1 << 30, v)) w.seq = (int)v;
+    else if (is("split") && number(val, 1, 1 << 30, v)) w.split_k = (int)v;
+    else if (is("work") && number(val, 0, 1, v)) w.work = (int)v;
+    else return false;
+  }
+  return true;
+}
+
+int dump_argv(char** a, int extra) {
   static const char* const layouts[] = {"kc", "mn"};
   static const char* const forms[] = {"static", "dyn", "mdev"};
   static const char* const precs[] = {"f32", "bf16x6", "bf16"};
@@ -187,7 +219,8 @@ int dump_argv(char** a) {
       !number(a[5], 1, big, lda) || lb < 0 || !number(a[7], 1, big, ldb) ||
       !number(a[8], NR_EPI_STORE, NR_EPI_SCATTER_ZEROED, epi) || form < 0 || prec < 0)
     return 2;
-  const Row w{a[0], M, N, K, Side{la, PLAIN, lda, 1, 0}, Side{lb, PLAIN, ldb, 1, 0}, (int)epi, 1, form, 0, 0, false};
+  Row w{a[0], M, N, K, Side{la, PLAIN, lda, 1, 0}, Side{lb, PLAIN, ldb, 1, 0}, (int)epi, 1, form, 0, 0, false};
+  if (!key_values(a + 11, extra, w)) return 2;
   dump(w, prec, precs[prec]);   // enum nr_gemm_precision follows the order of precs
   return 0;
 }
@@ -196,8 +229,10 @@ int dump_argv(char** a) {
 
 int main(int argc, char** argv) {
   if (argc > 1) {
-    const int rc = argc == 12 ? dump_argv(argv + 1) : 2;
-    if (rc) fprintf(stderr, "usage: %s [NAME M N K kc|mn A_LD kc|mn B_LD EPILOGUE static|dyn|mdev f32|bf16x6|bf16]\n", argv[0]);
+    const int rc = argc >= 12 ? dump_argv(argv + 1, argc - 12) : 2;
+    if (rc)
+      fprintf(stderr, "usage: %s [NAME M N K kc|mn A_LD kc|mn B_LD EPILOGUE static|dyn|mdev f32|bf16x6|bf16 "
+              "[amap=|bmap=plain|gather|conv3 aseg= bseg= cmap=gather|conv3 cseg= seq= split= work=0|1]]\n", argv[0]);
     return rc;
   }
   for (const Row& w : ROWS_TABLE) {

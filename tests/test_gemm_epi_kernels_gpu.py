@@ -25,11 +25,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import gemm_epi_util as U
+from gemm_guard_util import NAN, Block, _bits
 from newsrec_amd import _lib as L
 from newsrec_amd import kernels as K
 
-NAN = float("nan")
-ROW0 = 4            # the window's first row in its block
 _DEV = {}           # operands on the GPU, per (shape, ...): uploaded once
 
 
@@ -44,10 +43,6 @@ def _own_memory_pool():
         yield
         _DEV.clear()
     del pool
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def _round4(n):
@@ -77,29 +72,6 @@ def _b_operand(shape, layout, n, k_live=None):
         _DEV[key] = t.cuda()
     t = _DEV[key]
     return K.operand(t[:, :shape.K], L.KCONTIG) if layout == "kc" else K.operand(t[:, :n], L.MNCONTIG)
-
-
-class Block:
-    """An [m, n] window inside a NaN-filled block of m + 8 rows, `ld` apart, at row 4 and column `col`."""
-
-    def __init__(self, m, n, ld, col, fill=None):
-        host = torch.full((m + 8, ld), NAN)
-        if fill is not None:
-            host[ROW0:ROW0 + m, col:col + n] = fill
-        self.m, self.n, self.col = m, n, col
-        self.dev = host.cuda()
-        self.before = _bits(host)
-        self.win = self.dev[ROW0:ROW0 + m, col:col + n]
-
-    def check(self, live, name):
-        """Everything but the first `live` rows of the window bit-identical to before; returns those rows."""
-        after = self.dev.cpu()
-        keep = torch.ones(after.shape, dtype=torch.bool)
-        keep[ROW0:ROW0 + live, self.col:self.col + self.n] = False
-        changed = (_bits(after) != self.before) & keep
-        assert not changed.any(), "%s: %d elements outside the live window changed, first at %s" % (
-            name, int(changed.sum()), changed.nonzero()[0].tolist())
-        return after[ROW0:ROW0 + live, self.col:self.col + self.n]
 
 
 def _run(kernel, epi, layout, n, ldc_odd=False, c_off=0, bias_off=0, aux_ld_odd=False, aux_off=0, k_dev=None,
