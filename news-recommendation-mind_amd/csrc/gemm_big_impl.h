@@ -83,15 +83,7 @@ struct BigKC {
     const int f = tid + 512 * i;
     uint16_t* q = lds + row_of(f) * SR + 4 * quad_of(f);
     const float4 x = v[S][i];
-    if constexpr (NP == 1) {
-      *reinterpret_cast<uint2*>(q) = hi4(x.x, x.y, x.z, x.w);
-    } else {
-      uint2 p0, p1, p2;
-      split4(x.x, x.y, x.z, x.w, p0, p1, p2);
-      *reinterpret_cast<uint2*>(q) = p0;
-      *reinterpret_cast<uint2*>(q + PL) = p1;
-      *reinterpret_cast<uint2*>(q + 2 * PL) = p2;
-    }
+    put_planes<NP>(q, PL, x.x, x.y, x.z, x.w);
   }
   template <int S, int NP>
   __device__ __forceinline__ void store(uint16_t* lds, int tid) const {
@@ -195,16 +187,7 @@ struct BigMN {
   }
   template <int NP>
   __device__ __forceinline__ void put(uint16_t* q, float a, float b) const {
-    constexpr int PL = R * SR;
-    if constexpr (NP == 1) {
-      *reinterpret_cast<uint32_t*>(q) = pk_bf16(a, b);
-    } else {
-      uint32_t hh, mm, ll;
-      split2(a, b, hh, mm, ll);
-      *reinterpret_cast<uint32_t*>(q) = hh;
-      *reinterpret_cast<uint32_t*>(q + PL) = mm;
-      *reinterpret_cast<uint32_t*>(q + 2 * PL) = ll;
-    }
+    put_planes<NP>(q, R * SR, a, b);
   }
   // Chunk (column group cg, k pair kp) writes its four rows 4cg .. 4cg + 3 as four ds_write_b32 per
   // plane.  At BK = 16 the row stride is 12 words, so row 4cg + i sits at bank 16 cg + 12 i + kp
@@ -314,16 +297,7 @@ __global__ __launch_bounds__(512, 1) void gemm_big_kernel(Args g) {
   __shared__ __attribute__((aligned(16))) uint16_t Bs[2 * NP * PB];
   constexpr bool IDX_AHEAD = AM == MN_GATHER || BMODE == MN_GATHER;
 
-  if (g.mdyn) {
-    const int64_t m = *g.mdyn;
-    g.M = m < g.M ? (m > 0 ? m : 0) : g.M;
-  }
-  if (g.kdyn) {
-    const int64_t k = *g.kdyn;
-    g.K = k < g.K ? (k > 0 ? k : 0) : g.K;
-    const int64_t kc = (g.K + g.splits - 1) / g.splits;
-    g.kchunk = kc > 0 ? (kc + 31) / 32 * 32 : 32;
-  }
+  clamp_extents(g);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, c = lane & 31;
   const int gn = (int)((g.N + BN - 1) / BN);
   const int ntiles = (int)((g.M + BM - 1) / BM) * gn;
@@ -344,8 +318,8 @@ __global__ __launch_bounds__(512, 1) void gemm_big_kernel(Args g) {
       // pieces through the workspace: one partial tile each, at most tail_cap of them
       if (TR && g.slab && p * r > g.tail_cap) p = g.tail_cap / r;
       if (p > 1) {
-        kc_tail = ((g.K + p - 1) / p + 31) / 32 * 32;
-        pieces = (int)((g.K + kc_tail - 1) / kc_tail);
+        kc_tail = k_chunk(g.K, p);
+        pieces = (int)k_chunks(g.K, kc_tail);
       }
     }
     if (pieces > 1) {
@@ -404,12 +378,7 @@ __global__ __launch_bounds__(512, 1) void gemm_big_kernel(Args g) {
 #pragma unroll
       for (int j = 0; j < BigMN<BM, MN_PLAIN, BK>::NC; ++j) cs[j][0] = cs[j][1] = cs[j][2] = cs[j][3] = 0.f;
     }
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-      for (int j = 0; j < TJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
     la.init(g.A, u.m0, g.M, tid);
     lb.init(g.B, u.n0, g.N, tid);
     // k-tile t is loaded into register set t % 2, three tiles ahead of its MFMAs: tile kt+3's loads
@@ -532,14 +501,7 @@ __global__ __launch_bounds__(512, 1) void gemm_big_kernel(Args g) {
               NR_MF(0, 0);
               ilv_hook(i, 6 * j + 5);
             } else {
-              if constexpr (NP == 3) {   // smallest terms first
-                NR_MF(2, 0);
-                NR_MF(1, 1);
-                NR_MF(0, 2);
-                NR_MF(1, 0);
-                NR_MF(0, 1);
-              }
-              NR_MF(0, 0);
+              mfma_planes<NP, TR>(acc[i][j], a[i & 1], b[j]);
             }
 #undef NR_MF
           }

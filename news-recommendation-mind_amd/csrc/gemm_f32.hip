@@ -305,7 +305,7 @@ int launch_generic(const GemmCall& c, const nrfast::GemmRoute& r) {
   Args g;
   g.M = p.M; g.N = p.N; g.K = p.K;
   g.A = to_op(p.A); g.B = to_op(p.B); g.Cm = to_op(p.c_rows);
-  g.C = c.C; g.ldc = c.ldc; g.bias = c.bias; g.epi = r.epi; g.pad_row = c.pad_row;
+  g.C = c.d.C; g.ldc = c.d.ldc; g.bias = c.d.bias; g.epi = r.epi; g.pad_row = c.d.pad_row;
   g.kchunk = r.kchunk;
   const int ak = p.A->layout == NR_KCONTIG, bk = p.B->layout == NR_KCONTIG;
   if (r.bm == 128 && r.bn == 128) return launch_kc<128, 128>(g, ak, bk, r.splits, c.stream);
@@ -314,27 +314,25 @@ int launch_generic(const GemmCall& c, const nrfast::GemmRoute& r) {
   return launch_kc<64, 64>(g, ak, bk, r.splits, c.stream);
 }
 
-// The one entry behind the four exported ones: validates, routes (gemm_route.h), launches.
+// The one path behind the five exported entries: gemm_prepare validates and routes (gemm_route.h) a
+// described call (`run` false: a valid call with nothing to do), gemm_launch runs the route;
+// nr_gemm_f32_pair prepares two calls before it launches either.
 // `dyn`: the dynamic form -- device-resident extents and / or a CU cap, fast kernels only; the static
 // form also takes unaligned operands (generic kernel) and small tiles.
-// gemm_prepare validates and routes (`run` false: a valid call with nothing to do), gemm_launch runs
-// the route; nr_gemm_f32_pair prepares two calls before it launches either.
-int gemm_prepare(bool dyn, int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C,
-                 int64_t ldc, const float* bias, int32_t epilogue, const nr_operand* c_rows, int64_t pad_row,
-                 int32_t split_k, const int32_t* m_dev, const int32_t* k_dev, int32_t prec, int32_t max_cus, float* work,
-                 int64_t work_elems, float* colsum, int32_t* colsum_folded, hipStream_t stream, GemmCall& c,
-                 nrfast::GemmRoute& r, bool& run) {
+int gemm_prepare(bool dyn, const nr_gemm_desc& d, hipStream_t stream, GemmCall& c, nrfast::GemmRoute& r, bool& run) {
+  const nr_operand *A = d.A, *B = d.B, *c_rows = d.c_rows;
+  const int32_t epilogue = d.epilogue;
   run = false;
-  if (work_elems < 0 || (work_elems > 0 && !work)) return NR_EINVAL(16);
-  if (colsum_folded) *colsum_folded = 0;
-  if (colsum && !colsum_folded) return NR_EINVAL(17);
-  if (dyn && max_cus < 0) return NR_EINVAL(15);
+  if (d.work_elems < 0 || (d.work_elems > 0 && !d.work)) return NR_EINVAL(16);
+  if (d.colsum_folded) *d.colsum_folded = 0;
+  if (d.colsum && !d.colsum_folded) return NR_EINVAL(17);
+  if (dyn && d.max_cus < 0) return NR_EINVAL(15);
   // the device K of the dynamic form must be a multiple of 32, so its bound must be one
-  if (M < 0 || N < 0 || K < 0 || (dyn && K % 32)) return NR_EINVAL(0);
+  if (d.M < 0 || d.N < 0 || d.K < 0 || (dyn && d.K % 32)) return NR_EINVAL(0);
   // (the two forms have always reported a bad prec under different argument numbers)
-  if (prec != NR_GEMM_F32 && prec != NR_GEMM_BF16X6 && prec != NR_GEMM_BF16) return NR_EINVAL(dyn ? 14 : 12);
+  if (d.prec != NR_GEMM_F32 && d.prec != NR_GEMM_BF16X6 && d.prec != NR_GEMM_BF16) return NR_EINVAL(dyn ? 14 : 12);
   if (epilogue < NR_EPI_STORE || epilogue > NR_EPI_SCATTER_ZEROED) return NR_EINVAL(3);
-  if (!A || !B || !C || !A->data || !B->data) return NR_EINVAL(1);
+  if (!A || !B || !d.C || !A->data || !B->data) return NR_EINVAL(1);
   // gathered tables must be float4-addressable; the dynamic form has the fast kernels only, which
   // need that of every operand
   if (((dyn || A->map != NR_ROWS_PLAIN) && (A->ld & 3)) || ((dyn || B->map != NR_ROWS_PLAIN) && (B->ld & 3)))
@@ -349,18 +347,18 @@ int gemm_prepare(bool dyn, int64_t M, int64_t N, int64_t K, const nr_operand* A,
   // the dynamic form checks the scatter-store rows here, the static form only once it has work to
   // do (after the split_k check and the empty-problem return)
   if (dyn && no_store_rows) return NR_EINVAL(4);
-  if (split_k < 1) split_k = 1;
+  const int32_t split_k = d.split_k < 1 ? 1 : d.split_k;
   if (split_k > 1 && epilogue != NR_EPI_ATOMIC && epilogue != NR_EPI_SCATTER) return NR_EINVAL(5);
   // K == 0: the dynamic form leaves C alone, the static form runs the generic kernel's epilogue on
   // zero accumulators (C = bias for a store epilogue)
-  if (M == 0 || N == 0 || (dyn && K == 0)) return NR_OK;
+  if (d.M == 0 || d.N == 0 || (dyn && d.K == 0)) return NR_OK;
   if (no_store_rows) return NR_EINVAL(4);
 
-  c = GemmCall{{M, N, K, A, B, c_rows, epilogue, split_k, prec, dyn, m_dev != nullptr, max_cus, work, work_elems,
-                colsum != nullptr},
-               C, ldc, bias, pad_row, m_dev, k_dev, work, colsum, colsum_folded, stream};
+  c = GemmCall{{d.M, d.N, d.K, A, B, c_rows, epilogue, split_k, d.prec, dyn, d.m_dev != nullptr, d.max_cus, d.work,
+                d.work_elems, d.colsum != nullptr},
+               d, stream};
   // the CU count matters to a route only where it sizes a workspace's use
-  r = nrfast::gemm_route(c.p, work ? nr_gemm_device_cus() : 0);
+  r = nrfast::gemm_route(c.p, d.work ? nr_gemm_device_cus() : 0);
   if (r.family == nrfast::GEMM_NOT_ELIGIBLE) return NR_EINVAL(r.einval);
   run = true;
   return NR_OK;
@@ -370,22 +368,15 @@ int gemm_launch(const GemmCall& c, const nrfast::GemmRoute& r) {
   return r.family == nrfast::GEMM_GENERIC ? launch_generic(c, r) : nr_gemm_fast(c, r);
 }
 
-int gemm_entry(bool dyn, int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C,
-               int64_t ldc, const float* bias, int32_t epilogue, const nr_operand* c_rows, int64_t pad_row,
-               int32_t split_k, const int32_t* m_dev, const int32_t* k_dev, int32_t prec, int32_t max_cus, float* work,
-               int64_t work_elems, float* colsum, int32_t* colsum_folded, hipStream_t stream) {
+// nr_gemm_f32_ws reads a description's form off it: m_dev, k_dev NULL and max_cus 0 is the static form
+bool desc_dyn(const nr_gemm_desc& d) { return d.m_dev || d.k_dev || d.max_cus != 0; }
+
+int gemm_run(bool dyn, const nr_gemm_desc& d, hipStream_t stream) {
   GemmCall c;
   nrfast::GemmRoute r;
   bool run;
-  const int rc = gemm_prepare(dyn, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec,
-                              max_cus, work, work_elems, colsum, colsum_folded, stream, c, r, run);
+  const int rc = gemm_prepare(dyn, d, stream, c, r, run);
   return rc != NR_OK || !run ? rc : gemm_launch(c, r);
-}
-
-int desc_prepare(const nr_gemm_desc* d, hipStream_t stream, GemmCall& c, nrfast::GemmRoute& r, bool& run) {
-  return gemm_prepare(d->m_dev || d->k_dev || d->max_cus != 0, d->M, d->N, d->K, d->A, d->B, d->C, d->ldc, d->bias,
-                      d->epilogue, d->c_rows, d->pad_row, d->split_k, d->m_dev, d->k_dev, d->prec, d->max_cus, d->work,
-                      d->work_elems, d->colsum, d->colsum_folded, stream, c, r, run);
 }
 
 }  // namespace
@@ -394,18 +385,19 @@ extern "C" int nr_gemm_f32(int64_t M, int64_t N, int64_t K, const nr_operand* A,
                            const nr_operand* B, float* C, int64_t ldc, const float* bias,
                            int32_t epilogue, const nr_operand* c_rows, int64_t pad_row,
                            int32_t split_k, int32_t prec, hipStream_t stream) {
-  return gemm_entry(false, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, nullptr, nullptr, prec, 0,
-                    nullptr, 0, nullptr, nullptr, stream);
+  return gemm_run(false, nr_gemm_desc{M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, nullptr, nullptr,
+                                      prec, 0, nullptr, 0, nullptr, nullptr},
+                  stream);
 }
 
-// m_dev, k_dev NULL and max_cus 0: the static form
 extern "C" int nr_gemm_f32_ws(int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B, float* C,
                               int64_t ldc, const float* bias, int32_t epilogue, const nr_operand* c_rows,
                               int64_t pad_row, int32_t split_k, const int32_t* m_dev, const int32_t* k_dev,
                               int32_t prec, int32_t max_cus, float* work, int64_t work_elems, float* colsum,
                               int32_t* colsum_folded, hipStream_t stream) {
-  return gemm_entry(m_dev || k_dev || max_cus != 0, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k,
-                    m_dev, k_dev, prec, max_cus, work, work_elems, colsum, colsum_folded, stream);
+  const nr_gemm_desc d{M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev,
+                       prec, max_cus, work, work_elems, colsum, colsum_folded};
+  return gemm_run(desc_dyn(d), d, stream);
 }
 
 // Two independent problems: one launch where gemm_pair_order (gemm_route.h) allows it, else the two
@@ -415,12 +407,12 @@ extern "C" int nr_gemm_f32_pair(const nr_gemm_desc* p1, const nr_gemm_desc* p2, 
   GemmCall c1, c2;
   nrfast::GemmRoute r1, r2;
   bool run1, run2;
-  int rc = desc_prepare(p1, stream, c1, r1, run1);
+  int rc = gemm_prepare(desc_dyn(*p1), *p1, stream, c1, r1, run1);
   if (rc != NR_OK) return rc;
-  rc = desc_prepare(p2, stream, c2, r2, run2);
+  rc = gemm_prepare(desc_dyn(*p2), *p2, stream, c2, r2, run2);
   if (rc != NR_OK) return rc <= -1000 ? rc - 100 : rc;   // NR_EINVAL(100 + n): problem 2's argument n
   if (run1 && run2) {
-    const nrfast::GemmOut o1{c1.C, c1.ldc, c1.bias}, o2{c2.C, c2.ldc, c2.bias};
+    const nrfast::GemmOut o1{c1.d.C, c1.d.ldc, c1.d.bias}, o2{c2.d.C, c2.d.ldc, c2.d.bias};
     if (nrfast::gemm_pair_alias(c1.p, o1, c2.p, o2)) return NR_EINVAL(201);
     const int order = nrfast::gemm_pair_order(c1.p, r1, o1, c2.p, r2, o2);
     if (order == 1) return nr_gemm_fast_pair(c1, r1, c2, r2);
@@ -437,14 +429,16 @@ extern "C" int nr_gemm_f32_dyn(int64_t M, int64_t N, int64_t K, const nr_operand
                                float* C, int64_t ldc, const float* bias, int32_t epilogue,
                                const nr_operand* c_rows, int64_t pad_row, int32_t split_k, const int32_t* m_dev,
                                const int32_t* k_dev, int32_t prec, hipStream_t stream) {
-  return gemm_entry(true, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec, 0,
-                    nullptr, 0, nullptr, nullptr, stream);
+  return gemm_run(true, nr_gemm_desc{M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec,
+                                     0, nullptr, 0, nullptr, nullptr},
+                  stream);
 }
 
 extern "C" int nr_gemm_f32_dyn_cus(int64_t M, int64_t N, int64_t K, const nr_operand* A, const nr_operand* B,
                                    float* C, int64_t ldc, const float* bias, int32_t epilogue,
                                    const nr_operand* c_rows, int64_t pad_row, int32_t split_k, const int32_t* m_dev,
                                    const int32_t* k_dev, int32_t prec, int32_t max_cus, hipStream_t stream) {
-  return gemm_entry(true, M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec,
-                    max_cus, nullptr, 0, nullptr, nullptr, stream);
+  return gemm_run(true, nr_gemm_desc{M, N, K, A, B, C, ldc, bias, epilogue, c_rows, pad_row, split_k, m_dev, k_dev, prec,
+                                     max_cus, nullptr, 0, nullptr, nullptr},
+                  stream);
 }

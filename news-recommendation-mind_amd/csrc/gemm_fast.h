@@ -2,16 +2,11 @@
 #pragma once
 #include "gemm_route.h"
 
-// One validated call: what gemm_route looks at plus the pointers only a launch needs.
+// One validated call: what gemm_route looks at (split_k at least 1 there), the caller's description
+// for the pointers only a launch needs, and the stream.
 struct GemmCall {
   nrfast::GemmProblem p;
-  float* C;
-  int64_t ldc;
-  const float* bias;
-  int64_t pad_row;
-  const int32_t *m_dev, *k_dev;
-  float *work, *colsum;
-  int32_t* colsum_folded;
+  nr_gemm_desc d;
   hipStream_t stream;
 };
 

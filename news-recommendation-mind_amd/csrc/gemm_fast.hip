@@ -31,22 +31,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(float* __restrict__ 
                                                             int64_t stride, int splits, int64_t M, int64_t N,
                                                             int64_t K, int64_t kchunk, const int32_t* mdyn,
                                                             const int32_t* kdyn, int vec, float* __restrict__ colsum) {
-  int64_t m_eff = M;
-  if (mdyn) {
-    const int64_t m = *mdyn;
-    m_eff = m < M ? (m > 0 ? m : 0) : M;
+  const int64_t m_eff = mdyn ? clamp_extent(M, *mdyn) : M;
+  if (kdyn) {   // as clamp_extents does in the GEMM kernel
+    K = clamp_extent(K, *kdyn);
+    kchunk = k_chunk(K, splits);
   }
-  int ns = splits;
-  if (kdyn) {
-    int64_t k = *kdyn;
-    k = k < K ? (k > 0 ? k : 0) : K;
-    const int64_t kc = (k + splits - 1) / splits;
-    const int64_t kch = kc > 0 ? (kc + 31) / 32 * 32 : 32;
-    ns = (int)((k + kch - 1) / kch);
-  } else {
-    ns = (int)((K + kchunk - 1) / kchunk);
-  }
-  ns = ns < splits ? ns : splits;
+  const int64_t nk = k_chunks(K, kchunk);
+  const int ns = nk < splits ? (int)nk : splits;
   const int64_t n4 = (N + 3) / 4, total = m_eff * n4;
   if (colsum) {   // the fused bias gradient: per-split column sums after the partial tiles
     const float* cs = slab + (int64_t)splits * stride;
@@ -89,11 +80,7 @@ __global__ __launch_bounds__(256) void tail_reduce_kernel(float* __restrict__ C,
   const int* hd = reinterpret_cast<const int*>(ws);
   const int full = hd[0], rem = hd[1], pieces = hd[2], gn = hd[3];
   if (pieces <= 1 || rem <= 0 || gn <= 0) return;
-  int64_t m_eff = M;
-  if (mdyn) {
-    const int64_t m = *mdyn;
-    m_eff = m < M ? (m > 0 ? m : 0) : M;
-  }
+  const int64_t m_eff = mdyn ? clamp_extent(M, *mdyn) : M;
   const float* part = ws + TAIL_WS_HDR;
   const int64_t total = (int64_t)rem * 256 * 64;   // float4 of the rem tail tiles
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
@@ -144,25 +131,25 @@ nrfast::Args make_args(const GemmCall& c, const nrfast::GemmRoute& r) {
   g.B = Op{B->data, B->ld, B->rows, B->seq_len, B->seg};
   g.Cm = Op{cr ? cr->data : nullptr, cr ? cr->ld : 0, cr ? cr->rows : nullptr,
             cr ? (cr->map == NR_ROWS_CONV3 ? cr->seq_len : 1) : 1, cr ? cr->seg : 1};
-  g.C = c.C; g.ldc = c.ldc; g.bias = c.bias; g.epi = r.epi; g.pad_row = c.pad_row;
-  g.mdyn = c.m_dev; g.kdyn = c.k_dev; g.max_cus = p.max_cus > 0 ? p.max_cus : 0;
+  g.C = c.d.C; g.ldc = c.d.ldc; g.bias = c.d.bias; g.epi = r.epi; g.pad_row = c.d.pad_row;
+  g.mdyn = c.d.m_dev; g.kdyn = c.d.k_dev; g.max_cus = p.max_cus > 0 ? p.max_cus : 0;
   g.splits = r.splits; g.kchunk = r.kchunk; g.tail = r.tail;
   {
-    bool v = p.N % 4 == 0 && c.ldc % 4 == 0 && aligned16(c.C) && (!c.bias || aligned16(c.bias));
+    bool v = p.N % 4 == 0 && c.d.ldc % 4 == 0 && aligned16(c.d.C) && (!c.d.bias || aligned16(c.d.bias));
     if (r.epi == NR_EPI_ACCUM_GATE || r.epi == NR_EPI_STORE_GELU || r.epi == NR_EPI_GELU_GRAD)
       v = v && cr && cr->ld % 4 == 0 && aligned16(cr->data);
     g.vec = v ? 1 : 0;
   }
   const int64_t sld = (p.N + 3) & ~int64_t(3);
   if (r.tail_ws) {
-    g.slab = c.work;
+    g.slab = c.d.work;
     g.tail_cap = r.tail_cap;
   }
   if (r.slab) {
-    g.slab = c.work;
+    g.slab = c.d.work;
     g.slab_ld = sld;
     g.slab_stride = p.M * sld;
-    g.colsum = r.fold ? c.colsum : nullptr;
+    g.colsum = r.fold ? c.d.colsum : nullptr;
   }
   return g;
 }
@@ -194,17 +181,17 @@ int nr_gemm_fast(const GemmCall& c, const nrfast::GemmRoute& r) {
   }
   if (rc != NR_OK) return rc;
   if (r.tail_ws) {
-    hipLaunchKernelGGL(tail_reduce_kernel, dim3(1024), dim3(256), 0, c.stream, c.C, c.ldc, c.work, g.Cm.idx,
-                       g.pad_row, p.M, c.m_dev, p.N, g.vec);
+    hipLaunchKernelGGL(tail_reduce_kernel, dim3(1024), dim3(256), 0, c.stream, c.d.C, c.d.ldc, c.d.work, g.Cm.idx,
+                       g.pad_row, p.M, c.d.m_dev, p.N, g.vec);
     NR_LAUNCH_CHECK();
   }
   if (r.slab) {
     int64_t blocks = (p.M * ((p.N + 3) / 4) + 255) / 256;
     blocks = blocks > 2048 ? 2048 : (blocks < 1 ? 1 : blocks);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, c.stream, c.C, c.ldc, c.work, sld,
-                       g.slab_stride, r.splits, p.M, p.N, p.K, r.kchunk, c.m_dev, c.k_dev, g.vec, g.colsum);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, c.stream, c.d.C, c.d.ldc, c.d.work, sld,
+                       g.slab_stride, r.splits, p.M, p.N, p.K, r.kchunk, c.d.m_dev, c.d.k_dev, g.vec, g.colsum);
     NR_LAUNCH_CHECK();
-    if (r.fold && c.colsum_folded) *c.colsum_folded = 1;
+    if (r.fold && c.d.colsum_folded) *c.d.colsum_folded = 1;
   }
   return NR_OK;
 }

@@ -46,6 +46,50 @@ __device__ __forceinline__ void split4(float a, float b, float c, float d, uint2
 __device__ __forceinline__ uint2 hi4(float a, float b, float c, float d) {
   return make_uint2(pk_bf16(a, b), pk_bf16(c, d));
 }
+// Four values (k consecutive) of one row -> its NP bf16 planes, plane_stride bf16 apart, one 8-B
+// store per plane (NP = 3: the bf16x6 terms h, m, l; NP = 1: the values rounded to bf16); and the
+// two-value form, one 4-B store per plane.
+template <int NP>
+__device__ __forceinline__ void put_planes(uint16_t* q, int plane_stride, float a, float b, float c, float d) {
+  if constexpr (NP == 1) {
+    *reinterpret_cast<uint2*>(q) = hi4(a, b, c, d);
+  } else {
+    uint2 p0, p1, p2;
+    split4(a, b, c, d, p0, p1, p2);
+    *reinterpret_cast<uint2*>(q) = p0;
+    *reinterpret_cast<uint2*>(q + plane_stride) = p1;
+    *reinterpret_cast<uint2*>(q + 2 * plane_stride) = p2;
+  }
+}
+template <int NP>
+__device__ __forceinline__ void put_planes(uint16_t* q, int plane_stride, float a, float b) {
+  if constexpr (NP == 1) {
+    *reinterpret_cast<uint32_t*>(q) = pk_bf16(a, b);
+  } else {
+    uint32_t h, m, l;
+    split2(a, b, h, m, l);
+    *reinterpret_cast<uint32_t*>(q) = h;
+    *reinterpret_cast<uint32_t*>(q + plane_stride) = m;
+    *reinterpret_cast<uint32_t*>(q + 2 * plane_stride) = l;
+  }
+}
+// acc += A B over one 16-deep step from the operands' planes: NP = 3 the six bf16x6 products, smallest
+// terms first; NP = 1 the one bf16 product.  TR: operands swapped (transposed accumulators).
+template <int NP, bool TR>
+__device__ __forceinline__ void mfma_planes(f32x16& acc, const bf16x8 (&a)[NP], const bf16x8 (&b)[NP]) {
+  auto mf = [&](int x, int y) {
+    acc = TR ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[y], a[x], acc, 0, 0, 0)
+             : __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x], b[y], acc, 0, 0, 0);
+  };
+  if constexpr (NP == 3) {
+    mf(2, 0);
+    mf(1, 1);
+    mf(0, 2);
+    mf(1, 0);
+    mf(0, 1);
+  }
+  mf(0, 0);
+}
 constexpr int SROW = 40;          // split LDS image: [plane][row][k] bf16, 32 k + 8 pad (80-B rows)
 constexpr int SPL = 128 * SROW;   // one plane of a 128-row operand tile
 
@@ -249,16 +293,7 @@ struct Loader {
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         const int f = tid + 256 * i;
-        uint16_t* q = lds + kc_row(f) * SROW + 4 * kc_quad(f);
-        if constexpr (NP == 1) {
-          *reinterpret_cast<uint2*>(q) = hi4(v[i].x, v[i].y, v[i].z, v[i].w);
-        } else {
-          uint2 p0, p1, p2;
-          split4(v[i].x, v[i].y, v[i].z, v[i].w, p0, p1, p2);
-          *reinterpret_cast<uint2*>(q) = p0;
-          *reinterpret_cast<uint2*>(q + SPL) = p1;
-          *reinterpret_cast<uint2*>(q + 2 * SPL) = p2;
-        }
+        put_planes<NP>(lds + kc_row(f) * SROW + 4 * kc_quad(f), SPL, v[i].x, v[i].y, v[i].z, v[i].w);
       }
     }
   }
@@ -322,26 +357,13 @@ struct MNBlk {
   }
 
   template <int NP>
-  __device__ __forceinline__ void put(uint16_t* q, float a, float b, float c, float e) const {
-    if constexpr (NP == 1) {
-      *reinterpret_cast<uint2*>(q) = hi4(a, b, c, e);
-    } else {
-      uint2 p0, p1, p2;
-      split4(a, b, c, e, p0, p1, p2);
-      *reinterpret_cast<uint2*>(q) = p0;
-      *reinterpret_cast<uint2*>(q + SPL) = p1;
-      *reinterpret_cast<uint2*>(q + 2 * SPL) = p2;
-    }
-  }
-
-  template <int NP>
   __device__ __forceinline__ void store_split(uint16_t* lds, int tid) const {
     const int kg = tid & 7, cg = tid >> 3;
     uint16_t* q = lds + (4 * cg) * SROW + 4 * kg;
-    put<NP>(q, v[0].x, v[1].x, v[2].x, v[3].x);
-    put<NP>(q + SROW, v[0].y, v[1].y, v[2].y, v[3].y);
-    put<NP>(q + 2 * SROW, v[0].z, v[1].z, v[2].z, v[3].z);
-    put<NP>(q + 3 * SROW, v[0].w, v[1].w, v[2].w, v[3].w);
+    put_planes<NP>(q, SPL, v[0].x, v[1].x, v[2].x, v[3].x);
+    put_planes<NP>(q + SROW, SPL, v[0].y, v[1].y, v[2].y, v[3].y);
+    put_planes<NP>(q + 2 * SROW, SPL, v[0].z, v[1].z, v[2].z, v[3].z);
+    put_planes<NP>(q + 3 * SROW, SPL, v[0].w, v[1].w, v[2].w, v[3].w);
   }
 };
 
@@ -600,6 +622,27 @@ struct Cursor {
   int kt;   // k-tile within the unit
   Unit u;
 };
+
+// Device-resident extents (row counts produced on the GPU, e.g. nr_unique_rows) into the kernel's own
+// copy of its arguments: the host sizes were upper bounds for the grid, and the K splits are re-cut over
+// the device K exactly as the host cut them over the bound (k_chunk, gemm_route.h).
+__device__ __forceinline__ void clamp_extents(Args& g) {
+  if (g.mdyn) g.M = clamp_extent(g.M, *g.mdyn);
+  if (g.kdyn) {
+    g.K = clamp_extent(g.K, *g.kdyn);
+    g.kchunk = k_chunk(g.K, g.splits);
+  }
+}
+
+template <int TI, int TJ>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[TI][TJ]) {
+#pragma unroll
+  for (int i = 0; i < TI; ++i)
+#pragma unroll
+    for (int j = 0; j < TJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
 
 // Resident-block slots (CUs x occupancy) of a persistent kernel of THREADS per workgroup, cached per
 // device.  Every kernel of one width has the same function type, so they share the cache: the first

@@ -27,99 +27,24 @@ __device__ __forceinline__ void gemm_fast_body(Args g, const int bid, const int 
   using LB = Loader<BN, BMODE>;
   constexpr bool IDX_AHEAD = AM == MN_GATHER || BMODE == MN_GATHER;
 
-  // device-resident extents (row counts produced on the GPU, e.g. nr_unique_rows): the host
-  // sizes were upper bounds for the grid
-  if (g.mdyn) {
-    const int64_t m = *g.mdyn;
-    g.M = m < g.M ? (m > 0 ? m : 0) : g.M;
-  }
-  if (g.kdyn) {
-    const int64_t k = *g.kdyn;
-    g.K = k < g.K ? (k > 0 ? k : 0) : g.K;
-    const int64_t kc = (g.K + g.splits - 1) / g.splits;
-    g.kchunk = kc > 0 ? (kc + 31) / 32 * 32 : 32;
-  }
+  clamp_extents(g);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, c = lane & 31;
   const int gn = (int)((g.N + BN - 1) / BN);
   const int ntiles = (int)((g.M + BM - 1) / BM) * gn;
   const int units = ntiles * g.splits;
-
-  // first non-empty unit at or after virtual id `id` in this block's sequence (a split past a
-  // device-resident K is empty), or `units`
-  auto skip_empty = [&](int id, Unit& u) -> int {
-    for (; id < units; id += G) {
-      u = decode_unit(g, id, units, ntiles, gn, BM, BN);
-      if (u.nt > 0) return id;
-    }
-    return units;
-  };
-  // cursor advance: false when the block's sequence is exhausted
-  auto advance = [&](Cursor& p) -> bool {
-    if (p.kt + 1 < p.u.nt) { ++p.kt; return true; }
-    Unit u;
-    const int nid = skip_empty(p.id + G, u);
-    if (nid >= units) return false;
-    p.id = nid;
-    p.kt = 0;
-    p.u = u;
-    return true;
-  };
-  auto kof = [](const Cursor& p) -> int64_t { return p.u.kbeg + (int64_t)p.kt * 32; };
-  auto peek_k = [&](const Cursor& p) -> int64_t {   // k of the position after p, or -1
-    if (p.kt + 1 < p.u.nt) return kof(p) + 32;
-    Unit u;
-    return skip_empty(p.id + G, u) < units ? u.kbeg : -1;
-  };
-
-  Cursor cp;   // compute position
-  cp.kt = 0;
-  cp.id = skip_empty(bid, cp.u);
-  if (cp.id >= units) return;
+#define NR_WALK_PART 1   // the unit walk: cp (or return), advance, peek_k
+#include "gemm_walk.h"
 
   constexpr int TI = BM / 64, TJ = BN / 64;
   const int wm = (w >> 1) * (BM / 2), wn = (w & 1) * (BN / 2);
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  LA la;
-  LB lb;
-  Cursor lp = cp;   // load position
-  la.init(g.A, lp.u.m0, g.M, tid);
-  lb.init(g.B, lp.u.n0, g.N, tid);
-  auto issue = [&](const Cursor& p) {
-    const int64_t k = kof(p);
-    la.load(g.A, p.u.m0, g.M, k, tid);
-    lb.load(g.B, p.u.n0, g.N, k, tid);
-    if (IDX_AHEAD) {   // token ids of the position after p, one load ahead of its data
-      const int64_t pk = peek_k(p);
-      if (pk >= 0) {
-        la.prefetch_idx(g.A, pk, g.K, tid);
-        lb.prefetch_idx(g.B, pk, g.K, tid);
-      }
-    }
-  };
-  auto step_load = [&]() -> bool {   // move lp one position and issue its loads
-    const int old = lp.id;
-    if (!advance(lp)) return false;
-    if (lp.id != old) {
-      la.init(g.A, lp.u.m0, g.M, tid);
-      lb.init(g.B, lp.u.n0, g.N, tid);
-    }
-    issue(lp);
-    return true;
-  };
+  zero_acc(acc);
 
   // prologue: P0 -> LDS[0], P1 -> registers
-  if (IDX_AHEAD) {
-    la.prefetch_idx(g.A, kof(lp), g.K, tid);
-    lb.prefetch_idx(g.B, kof(lp), g.K, tid);
-  }
-  issue(lp);
+  LA la;
+  LB lb;
+#define NR_WALK_PART 2   // the load position: lp, step_load; P0's loads issued
+#include "gemm_walk.h"
   la.store(As[0], tid);
   lb.store(Bs[0], tid);
   bool staged = step_load();   // registers hold the position after cp
@@ -131,12 +56,7 @@ __device__ __forceinline__ void gemm_fast_body(Args g, const int bid, const int 
   for (;;) {
     if (pending) {   // previous unit's output, behind this unit's first loads
       epilogue_any<TR, TI, TJ>(g, acc, pm0, pn0, wm, wn, h, c);
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+      zero_acc(acc);
       pending = false;
     }
     const float* a_s = As[buf];

@@ -77,15 +77,34 @@ struct GemmRoute {
   int tail_cap = 0;         // which holds this many partial tiles
 };
 
+// The two rules the host and the kernels must read alike (the kernels and the reduce kernels re-derive
+// them from device-resident extents): callable from both under hipcc, plain functions under g++.
+#ifdef __HIPCC__
+#define NR_HD __host__ __device__
+#else
+#define NR_HD
+#endif
+
+// Length of one split of K cut `splits` ways: whole 32-deep k-tiles, never 0.
+NR_HD inline int64_t k_chunk(int64_t K, int64_t splits) {
+  const int64_t kc = (K + splits - 1) / splits;
+  return kc > 0 ? (kc + 31) / 32 * 32 : 32;
+}
+// Splits of length kchunk that hold some of K (a split that starts at or past K is empty).
+NR_HD inline int64_t k_chunks(int64_t K, int64_t kchunk) { return (K + kchunk - 1) / kchunk; }
+// A device-resident extent under its host bound: [0, bound].
+NR_HD inline int64_t clamp_extent(int64_t bound, int64_t dev_value) {
+  return dev_value < bound ? (dev_value > 0 ? dev_value : 0) : bound;
+}
+
 // K split `want` ways in 32-deep k-tiles: the chunk per split and the splits that are not empty.
 struct KSplit {
   int64_t kchunk;
   int splits;
 };
 inline KSplit k_split(int64_t K, int64_t want) {
-  int64_t kc = ((K + want - 1) / want + 31) / 32 * 32;
-  if (kc == 0) kc = 32;
-  const int s = (int)((K + kc - 1) / kc);
+  const int64_t kc = k_chunk(K, want);
+  const int s = (int)k_chunks(K, kc);
   return {kc, s > 0 ? s : 1};
 }
 

@@ -26,94 +26,25 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(Args g) {
   __shared__ __attribute__((aligned(16))) uint16_t Bs[NP * SPL];
   constexpr bool IDX_AHEAD = AM == MN_GATHER || BMODE == MN_GATHER;
 
-  if (g.mdyn) {
-    const int64_t m = *g.mdyn;
-    g.M = m < g.M ? (m > 0 ? m : 0) : g.M;
-  }
-  if (g.kdyn) {
-    const int64_t k = *g.kdyn;
-    g.K = k < g.K ? (k > 0 ? k : 0) : g.K;
-    const int64_t kc = (g.K + g.splits - 1) / g.splits;
-    g.kchunk = kc > 0 ? (kc + 31) / 32 * 32 : 32;
-  }
+  clamp_extents(g);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, c = lane & 31;
   const int gn = (int)((g.N + BN - 1) / BN);
   const int ntiles = (int)((g.M + BM - 1) / BM) * gn;
   const int units = ntiles * g.splits;
   const int G = gridDim.x;
-
-  auto skip_empty = [&](int id, Unit& u) -> int {
-    for (; id < units; id += G) {
-      u = decode_unit(g, id, units, ntiles, gn, BM, BN);
-      if (u.nt > 0) return id;
-    }
-    return units;
-  };
-  auto advance = [&](Cursor& p) -> bool {
-    if (p.kt + 1 < p.u.nt) { ++p.kt; return true; }
-    Unit u;
-    const int nid = skip_empty(p.id + G, u);
-    if (nid >= units) return false;
-    p.id = nid;
-    p.kt = 0;
-    p.u = u;
-    return true;
-  };
-  auto kof = [](const Cursor& p) -> int64_t { return p.u.kbeg + (int64_t)p.kt * 32; };
-  auto peek_k = [&](const Cursor& p) -> int64_t {
-    if (p.kt + 1 < p.u.nt) return kof(p) + 32;
-    Unit u;
-    return skip_empty(p.id + G, u) < units ? u.kbeg : -1;
-  };
-
-  Cursor cp;
-  cp.kt = 0;
-  cp.id = skip_empty(blockIdx.x, cp.u);
-  if (cp.id >= units) return;
+  const unsigned bid = blockIdx.x;
+#define NR_WALK_PART 1   // the unit walk: cp (or return), advance, peek_k
+#include "gemm_walk.h"
 
   constexpr int TI = 2, TJ = 2;
   const int wm = (w >> 1) * (BM / 2), wn = (w & 1) * (BN / 2);
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   LA la;
   LB lb;
-  Cursor lp = cp;
-  la.init(g.A, lp.u.m0, g.M, tid);
-  lb.init(g.B, lp.u.n0, g.N, tid);
-  auto issue = [&](const Cursor& p) {
-    const int64_t k = kof(p);
-    la.load(g.A, p.u.m0, g.M, k, tid);
-    lb.load(g.B, p.u.n0, g.N, k, tid);
-    if (IDX_AHEAD) {
-      const int64_t pk = peek_k(p);
-      if (pk >= 0) {
-        la.prefetch_idx(g.A, pk, g.K, tid);
-        lb.prefetch_idx(g.B, pk, g.K, tid);
-      }
-    }
-  };
-  auto step_load = [&]() -> bool {
-    const int old = lp.id;
-    if (!advance(lp)) return false;
-    if (lp.id != old) {
-      la.init(g.A, lp.u.m0, g.M, tid);
-      lb.init(g.B, lp.u.n0, g.N, tid);
-    }
-    issue(lp);
-    return true;
-  };
-
-  if (IDX_AHEAD) {
-    la.prefetch_idx(g.A, kof(lp), g.K, tid);
-    lb.prefetch_idx(g.B, kof(lp), g.K, tid);
-  }
-  issue(lp);
+#define NR_WALK_PART 2   // the load position: lp, step_load; P0's loads issued
+#include "gemm_walk.h"
   la.template store_split<NP>(As, tid);
   lb.template store_split<NP>(Bs, tid);
   bool staged = step_load();
@@ -124,12 +55,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(Args g) {
   for (;;) {
     if (pending) {
       epilogue_any<TR, TI, TJ>(g, acc, pm0, pn0, wm, wn, h, c);
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+      zero_acc(acc);
       pending = false;
     }
     const uint16_t* a_s = As;
@@ -149,23 +75,10 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(Args g) {
 #pragma unroll
         for (int p = 0; p < NP; ++p)
           b[j][p] = *reinterpret_cast<const bf16x8*>(b_s + p * SPL + (wn + 32 * j + c) * SROW + ko);
-#define NR_MF(X, Y)                                                                              \
-  acc[i][j] = TR ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j][Y], a[i][X], acc[i][j], 0, 0, 0) \
-                 : __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][X], b[j][Y], acc[i][j], 0, 0, 0)
 #pragma unroll
       for (int i = 0; i < TI; ++i)
 #pragma unroll
-        for (int j = 0; j < TJ; ++j) {
-          if constexpr (NP == 3) {   // smallest terms first
-            NR_MF(2, 0);
-            NR_MF(1, 1);
-            NR_MF(0, 2);
-            NR_MF(1, 0);
-            NR_MF(0, 1);
-          }
-          NR_MF(0, 0);
-        }
-#undef NR_MF
+        for (int j = 0; j < TJ; ++j) mfma_planes<NP, TR>(acc[i][j], a[i], b[j]);
     }
     __syncthreads();                // every wave is done reading P
     const int old = cp.id;

@@ -41,14 +41,7 @@ __device__ __forceinline__ Planes<NP> planes8(const float* x) {
 // acc += A B over one 16-deep step (smallest terms first)
 template <int NP>
 __device__ __forceinline__ void mfma_x(f32x16& acc, const Planes<NP>& a, const Planes<NP>& b) {
-  if constexpr (NP == 3) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[2], b.v[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[1], b.v[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[0], b.v[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[1], b.v[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[0], b.v[1], acc, 0, 0, 0);
-  }
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[0], b.v[0], acc, 0, 0, 0);
+  nrfast::mfma_planes<NP, false>(acc, a.v, b.v);
 }
 
 // acc += Σ_s A[s] B[s] over 16 register values per lane (the f32 form's 16 k-steps of 32x32x2):

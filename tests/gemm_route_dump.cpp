@@ -167,7 +167,8 @@ const Row ROWS_TABLE[] = {
 // split_k is 1 and there is no workspace.  The keys: amap / bmap = plain | gather | conv3 (the operands'
 // row maps) with aseg / bseg (CONV3: columns per tap); cmap = gather | conv3 with cseg (the scatter
 // epilogues' destination map); seq (tokens per title of every CONV3 map, default 30); split (split_k);
-// work = 0 | 1 (nr_gemm_splitk_workspace() floats of workspace).  Anything else: usage on stderr, exit 2.
+// work = 0 | 1 (nr_gemm_splitk_workspace() floats of workspace); cus (max_cus of the dynamic forms).
+// Anything else: usage on stderr, exit 2.
 int pick(const char* s, const char* const* names, int n) {
   for (int i = 0; i < n; ++i)
     if (!strcmp(s, names[i])) return i;
@@ -202,6 +203,7 @@ bool key_values(char** kv, int n, Row& w) {
     else if (is("seq") && number(val, 1, 1 << 30, v)) w.seq = (int)v;
     else if (is("split") && number(val, 1, 1 << 30, v)) w.split_k = (int)v;
     else if (is("work") && number(val, 0, 1, v)) w.work = (int)v;
+    else if (is("cus") && number(val, 0, 1 << 20, v)) w.max_cus = (int)v;
     else return false;
   }
   return true;
@@ -225,9 +227,23 @@ int dump_argv(char** a, int extra) {
   return 0;
 }
 
+// The one argument `ksplit`: the K-split rule the host and the kernels share, one line per (K, want):
+//   K want k_chunk(K, want) k_split(K, want).kchunk k_split(K, want).splits k_chunk(K, that .splits)
+int dump_ksplit() {
+  const int64_t Ks[] = {32, 64, 96, 480, 1152, 20832};
+  for (int64_t K : Ks)
+    for (int64_t want = 1; want <= 64; ++want) {
+      const KSplit ks = k_split(K, want);
+      printf("%lld %lld %lld %lld %d %lld\n", (long long)K, (long long)want, (long long)k_chunk(K, want),
+             (long long)ks.kchunk, ks.splits, (long long)k_chunk(K, ks.splits));
+    }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc == 2 && !strcmp(argv[1], "ksplit")) return dump_ksplit();
   if (argc > 1) {
     const int rc = argc >= 12 ? dump_argv(argv + 1, argc - 12) : 2;
     if (rc)

@@ -152,16 +152,53 @@ small_static f32: f32_64 tile=64x64 planes=0 modes=0,0 tr=1 epi=0 splits=1 kchun
 
 
 @pytest.fixture(scope="module")
-def dumped(tmp_path_factory):
+def route_exe(tmp_path_factory):
     cxx = shutil.which("g++")
     assert cxx, "g++ is needed to build tests/gemm_route_dump.cpp"
     exe = str(tmp_path_factory.mktemp("route") / "gemm_route_dump")
     subprocess.run([cxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=undefined", SRC, "-o", exe], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    return exe
+
+
+def _lines(exe, *args):
+    r = subprocess.run([exe] + list(args), capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stderr == ""   # no sanitizer report
     return r.stdout.splitlines()
+
+
+@pytest.fixture(scope="module")
+def dumped(route_exe):
+    return _lines(route_exe)
+
+
+def test_k_split_rule(route_exe):
+    """k_chunk / k_split (gemm_route.h), the one K-split rule of the host and the kernels, over
+    K in {32, 64, 96, 480, 1152, 20832} x want in 1..64: k_chunk is ceil32(ceil(K / want)) (32 when
+    that is 0); k_split takes that chunk and counts the splits that hold some of K; and the chunk the
+    kernels recompute from the route's split count (clamp_extents, splitk_reduce_kernel) is the
+    route's own chunk."""
+    rows = [tuple(int(x) for x in l.split()) for l in _lines(route_exe, "ksplit")]
+    assert [(k, w) for k, w, *_ in rows] == [(k, w) for k in (32, 64, 96, 480, 1152, 20832) for w in range(1, 65)]
+    for K, want, chunk, ks_chunk, ks_splits, chunk_of_splits in rows:
+        formula = -(-(-(-K // want)) // 32) * 32 or 32
+        assert chunk == formula, (K, want)
+        assert ks_chunk == chunk, (K, want)
+        assert ks_splits == -(-K // ks_chunk), (K, want)
+        assert chunk_of_splits == ks_chunk, (K, want, ks_splits)
+
+
+def test_walk_cases_route_where_they_say(route_exe):
+    """The multi-unit cases of tests/test_gemm_walk_gpu.py land on the kernel family, tile, planes,
+    operand modes and split count their table names (tests/gemm_walk_util.py)."""
+    import gemm_epi_util as U
+    import gemm_walk_util as W
+    for case in W.ALL_CASES:
+        lines = _lines(route_exe, *W.route_argv(case))
+        assert len(lines) == 1
+        got, want = U.parse_route(lines[0]), W.route_fields(case)
+        assert {f: got.get(f) for f in want} == want, (case.id, got)
 
 
 def test_routes_match_the_recorded_table(dumped):
