@@ -479,6 +479,49 @@ int nr_rnn_bwd(int32_t cell, const float* whh, const float* gates, const float* 
                int64_t B, int32_t N, int32_t H, const float* dhout, int64_t lddho, float* dgi,
                float* dgh, int64_t lddg, float* dh0, int64_t lddh0, hipStream_t stream);
 
+/* ------------------------------------------------------------------ bidirectional-LSTM news encoder */
+
+/* Sequential part of RNN_Encoder (RNN.py:5-33): nn.LSTM(E, H, batch_first, bidirectional) over nseq
+ * titles of L tokens, h0 = c0 = 0, ALL L steps run (no packing, no mask).  A workgroup owns a tile of
+ * 16 sequences of one direction; the step product runs on the exact-f32 MFMA.  With
+ * UT = ceil(H / 4), RT = ceil(H / 16), ntile = ceil(nseq / 16) and W_d = weight_hh_l0 (d = 0) /
+ * weight_hh_l0_reverse (d = 1), rows i,f,g,o:
+ *   gx       [nseq*L][8H] (ld ldgx >= 8H): columns [0,4H) x W_ih^T + b_ih of the forward direction,
+ *            [4H,8H) of the reverse direction
+ *   whh_fwd  [2][UT][UT][64] W_hh packed in MFMA lane order: element [d][T][ks][l] is
+ *            W_d[(l & 3) * H + u][k] with u = 4T + ((l & 15) >> 2), k = 4ks + (l >> 4); 0 where u or k >= H
+ *   whh_bwd  [2][RT][4*UT][64]: element [d][R][ks][l] is W_d[(l >> 4) * H + ks][16R + (l & 15)];
+ *            0 where ks or the column >= H
+ *   bhh      [2][4H] or NULL (zeros)
+ * Forward outputs: news [nseq][H] (ld ldn) = 1/2 (h->_{L-1} + h<-_0); tok [nseq*L][H] (ld ldt)
+ * = 1/2 (h->_t + h<-_t), or NULL: then nothing per step is written beyond the saved state.
+ * Saved state (written in full, every element defined):
+ *   gates  [2][ntile][L][UT][5][64]  i, f, g, o activated and c_{t-1} of (unit 4T + (l >> 4),
+ *          sequence 16*tile + (l & 15)) at token t; zeros for units >= H and sequences >= nseq
+ *   hprev  [2][nseq*L][ldh], columns [0,H): h_{t-1} of the direction at token t (the dW_hh operand;
+ *          columns [H, ldh) are never written)
+ *   hlast  [2][nseq][H]: each direction's final state
+ * The 1/2 (-> + <-) sums are formed by a second kernel of the same call: no atomics, two calls on the
+ * same inputs give the same bits.
+ * Errors (before any HIP call): -1000 nseq < 0, L < 1, H < 1, H > 256, ldgx < 8H, ldh < H, ldn < H,
+ * tok given with ldt < H; -1001 gx, whh_fwd, gates, hprev, hlast or news NULL.  nseq == 0 returns 0
+ * without a launch. */
+int nr_birnn_fwd(const float* gx, int64_t ldgx, const float* whh_fwd, const float* bhh, int64_t nseq,
+                 int32_t L, int32_t H, float* gates, float* hprev, int64_t ldh, float* hlast,
+                 float* news, int64_t ldn, float* tok, int64_t ldt, hipStream_t stream);
+
+/* Exact BPTT of nr_birnn_fwd from its saved gates, given dnews [nseq][H] (ld lddn) and / or dtok
+ * [nseq*L][H] (ld lddt), either NULL but not both.  Writes dg [nseq*L][8H] (ld lddg >= 8H), the
+ * pre-activation gate gradients of both directions in gx's column order (for an LSTM the input-path
+ * and recurrent-path gradients are equal): columns [0,8H) of every row are written, the caller zeroes
+ * nothing; columns past 8H are left alone.  No atomics.
+ * Errors (before any HIP call): -1000 nseq < 0, L < 1, H < 1, H > 256, lddg < 8H, a given dnews /
+ * dtok with lddn / lddt < H; -1001 whh_bwd, gates or dg NULL, or dnews and dtok both NULL.
+ * nseq == 0 returns 0 without a launch. */
+int nr_birnn_bwd(const float* whh_bwd, const float* gates, int64_t nseq, int32_t L, int32_t H,
+                 const float* dnews, int64_t lddn, const float* dtok, int64_t lddt, float* dg,
+                 int64_t lddg, hipStream_t stream);
+
 /* ------------------------------------------------------------------ scorer, optimizer, misc */
 
 enum nr_score_mode { NR_SCORE_RAW = 0, NR_SCORE_LOG_SOFTMAX = 1, NR_SCORE_SIGMOID = 2 };

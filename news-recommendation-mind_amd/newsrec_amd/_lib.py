@@ -113,6 +113,9 @@ _SIGS = {
                    c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr],
     "nr_rnn_bwd": [c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_i32, c_i64, c_i32, c_i32, c_ptr, c_i64,
                    c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr],
+    "nr_birnn_fwd": [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
+                     c_ptr, c_i64, c_ptr],
+    "nr_birnn_bwd": [c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr],
     "nr_score_fwd": [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_i32, c_i32, c_i32, c_ptr, c_ptr],
     "nr_score_bwd": [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_i32, c_ptr, c_i64, c_ptr,
                      c_i64, c_ptr],

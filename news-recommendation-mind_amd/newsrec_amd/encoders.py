@@ -15,7 +15,7 @@ from torch import nn
 from . import _lib as L
 from .attention import MultiheadAttention
 from . import functions as F
-from .functions import AttnPoolFn, CNNNewsFn, CNNNewsRowsFn, MHAFn, MHANewsFn, RNNUserFn
+from .functions import AttnPoolFn, CNNNewsFn, CNNNewsRowsFn, MHAFn, MHANewsFn, RNNNewsFn, RNNUserFn
 
 # fast eval: the MHA user encoder and its pooling in one launch (nr_mha_user_pool_fwd); False runs the
 # attention core and the pooling as two launches (the form the parity tests compare it with)
@@ -144,6 +144,42 @@ class MHA_Encoder(nn.Module):
         rows = news_embedding.reshape(-1, e).contiguous()
         if attn_mask is None:
             attn_mask = torch.ones(lead + (seq_len,), dtype=torch.uint8, device=rows.device)
+        return self.encode_tokens(rows, _identity_rows(rows.shape[0], rows.device).view(*lead, seq_len),
+                                  attn_mask, pad_row=-1, want_tokens=True)
+
+
+class RNN_Encoder(nn.Module):
+    """models/Encoders/RNN.py:5-33: a bidirectional LSTM over the title's tokens, h0 = c0 = 0.
+    token_repr = the mean of the two directions' outputs per token, news_repr = the mean of their
+    final states.  ``attn_mask`` is accepted so that TwoTower can call the encoder like the others
+    and is IGNORED, as in the reference's arithmetic: all L steps run, there is no packing, and a
+    padding token is an ordinary input (its embedding is the table's zero row)."""
+
+    def __init__(self, manager):
+        super().__init__()
+        self.hidden_dim = manager.hidden_dim
+        self.embedding_dim = manager.embedding_dim
+        self.rnn = nn.LSTM(self.embedding_dim, self.hidden_dim, batch_first=True, bidirectional=True)
+        for name, param in self.rnn.named_parameters():
+            if "weight" in name:
+                nn.init.orthogonal_(param)
+
+    def encode_tokens(self, table, token_ids, attn_mask=None, pad_row=0, want_tokens=False):
+        lead = token_ids.shape[:-1]
+        seq_len = token_ids.shape[-1]
+        T = token_ids.numel()
+        r = self.rnn
+        news, tok = RNNNewsFn.apply(table, token_ids.reshape(T), r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0,
+                                    r.bias_hh_l0, r.weight_ih_l0_reverse, r.weight_hh_l0_reverse,
+                                    r.bias_ih_l0_reverse, r.bias_hh_l0_reverse, seq_len, pad_row, want_tokens)
+        tok = tok.reshape(*lead, seq_len, self.hidden_dim) if tok is not None else None
+        return tok, news.reshape(*lead, self.hidden_dim)
+
+    def forward(self, news_embedding, attn_mask=None):
+        L.require_gpu(news_embedding)
+        lead = news_embedding.shape[:-2]
+        seq_len, e = news_embedding.shape[-2:]
+        rows = news_embedding.reshape(-1, e).contiguous()
         return self.encode_tokens(rows, _identity_rows(rows.shape[0], rows.device).view(*lead, seq_len),
                                   attn_mask, pad_row=-1, want_tokens=True)
 

@@ -1091,6 +1091,85 @@ class RNNUserFn(_GradAwareFn):
         return dx, dw_ih, dw_hh, db_ih, db_hh, dtab, None, None, None, None, None, None
 
 
+# ---------------------------------------------------------------------- bidirectional-LSTM news encoder
+
+class RNNNewsFn(_GradAwareFn):
+    """RNN_Encoder.forward (models/Encoders/RNN.py:17-33) on gathered token rows: the input projections
+    of both directions are ONE GEMM [T, 8H, E] (gather fused, b_ih in the epilogue), then the batched
+    recurrence nr_birnn_fwd.  All L steps run, padding tokens are ordinary inputs (there is no mask).
+    Returns (news [n, H], tok [T, H] or None)."""
+
+    @staticmethod
+    def forward(ctx, table, ids, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, seq_len, pad_row,
+                want_tokens):
+        # an unused token output must not cost a zero-filled gradient
+        ctx.set_materialize_grads(False)
+        ctx.prec = K.get_gemm_precision()
+        T = ids.numel()
+        n = T // seq_len
+        H = w_hh.shape[1]
+        GH = 8 * H
+        dev = table.device
+        w_cat = torch.cat([w_ih.detach(), w_ih_r.detach()], 0)            # [8H, E]
+        b_cat = torch.cat([b_ih.detach(), b_ih_r.detach()], 0)
+        bhh = torch.stack([b_hh.detach(), b_hh_r.detach()])
+        gx = _empty(T, GH, table)
+        K.gemm(T, GH, table.shape[1], K.operand(table, L.KCONTIG, rows=ids, mapping=L.ROWS_GATHER),
+               K.operand(w_cat, L.KCONTIG), gx, bias=b_cat)
+        whh_f, whh_b = K.birnn_pack_whh(w_hh, w_hh_r)
+        gates = torch.empty(K.birnn_gates_numel(n, seq_len, H), device=dev)
+        # h_{t-1} of both directions, rows padded with zero columns to a multiple of 32 (the dW_hh operand)
+        Hp = _ceil32(H)
+        hprev = torch.empty(2, T, Hp, device=dev)
+        if Hp != H:
+            hprev[:, :, H:].zero_()
+        hlast = torch.empty(2, n, H, device=dev)
+        news = _empty(n, H, table)
+        tok = _empty(T, H, table) if want_tokens else None
+        K.birnn_fwd(gx, whh_f, bhh, n, seq_len, H, gates, hprev, hlast, news, tok=tok)
+        ctx.save_for_backward(table, ids, w_cat, whh_b, gates, hprev)
+        ctx.cfg = (seq_len, pad_row, H)
+        ctx.table_ref = table
+        return news, tok
+
+    @staticmethod
+    @_gemm_backward
+    def backward(ctx, dnews, dtok):
+        table, ids, w_cat, whh_b, gates, hprev = ctx.saved_tensors
+        _word_row_flags(ctx.table_ref, None, None)
+        seq_len, pad_row, H = ctx.cfg
+        T = ids.numel()
+        n = T // seq_len
+        V, E = table.shape
+        GH = 8 * H
+        dev = table.device
+        if dnews is None and dtok is None:
+            return (None,) * 13
+        # the gate gradients with zero columns up to a multiple of 32: the table dgrad contracts over them
+        GHp = _ceil32(GH)
+        dg_full = torch.empty(T, GHp, device=dev)
+        if GHp != GH:
+            dg_full[:, GH:].zero_()
+        dg = dg_full[:, :GH]
+        K.birnn_bwd(whh_b, gates, n, seq_len, H, dg, dnews=dnews.contiguous() if dnews is not None else None,
+                    dtok=dtok.contiguous() if dtok is not None else None)
+        dw_cat, db_cat, dw_hh, dw_hh_r = _zeros_views(dev, (GH, E), (GH,), (4 * H, H), (4 * H, H))
+        _proj_wgrad(dg, K.operand(table, L.MNCONTIG, rows=ids, mapping=L.ROWS_GATHER), dw_cat, db_cat, T)
+        _proj_wgrad(dg[:, :4 * H], K.operand(hprev[0], L.MNCONTIG), dw_hh, None, T)
+        _proj_wgrad(dg[:, 4 * H:], K.operand(hprev[1], L.MNCONTIG), dw_hh_r, None, T)
+        dtable = None
+        if ctx.needs_input_grad[0]:
+            dtable = table_grad_buffer(ctx.table_ref, V, E, dev, zero=True)
+            w_p = w_cat if GHp == GH else torch.cat([w_cat, w_cat.new_zeros(GHp - GH, E)], 0)
+            K.gemm(T, E, GHp, K.operand(dg_full, L.KCONTIG), K.operand(w_p, L.MNCONTIG), dtable,
+                   epilogue=L.EPI_SCATTER, c_rows=K.rows_map(ids, L.ROWS_GATHER), pad_row=pad_row)
+            if TABLE_GRAD_HOOK(ctx.table_ref, dtable):
+                dtable = None
+        db_hh = db_cat.clone()   # the recurrent bias enters the same pre-activations as b_ih
+        return (dtable, None, dw_cat[:4 * H], dw_hh, db_cat[:4 * H], db_hh[:4 * H], dw_cat[4 * H:], dw_hh_r,
+                db_cat[4 * H:], db_hh[4 * H:], None, None, None)
+
+
 # ---------------------------------------------------------------------- scorer
 
 class ScoreFn(torch.autograd.Function):

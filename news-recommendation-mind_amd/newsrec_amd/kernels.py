@@ -706,6 +706,89 @@ def rnn_bwd(cell, whh, gates, hprev, cprev, B, N, H, dhout, dgi, dgh=None, dh0=N
            dh0.stride(0) if dh0 is not None else 0, L.stream_ptr(dhout))
 
 
+BIRNN_MAX_H = 256
+BIRNN_TILE = 16
+
+
+def birnn_gates_numel(nseq, seq_len, H):
+    """Floats of nr_birnn_fwd's saved gates: [2][ceil(nseq/16)][L][ceil(H/4)][5][64]."""
+    return 2 * ((nseq + BIRNN_TILE - 1) // BIRNN_TILE) * seq_len * ((H + 3) // 4) * 5 * 64
+
+
+def birnn_pack_whh(w_hh, w_hh_reverse):
+    """weight_hh_l0 / weight_hh_l0_reverse [4H, H] -> (whh_fwd [2, UT, UT, 64], whh_bwd [2, RT, 4UT, 64]),
+    the MFMA lane-order operands of nr_birnn_fwd / nr_birnn_bwd (include/newsrec_hip.h); zero padded."""
+    _f32(w_hh, w_hh_reverse)
+    H = w_hh.shape[1]
+    if tuple(w_hh.shape) != (4 * H, H) or w_hh_reverse.shape != w_hh.shape:
+        raise L.HipError("birnn_pack_whh: expected two [4H, H] matrices")
+    UT, RT = (H + 3) // 4, (H + 15) // 16
+    w = torch.stack([w_hh.detach(), w_hh_reverse.detach()]).view(2, 4, H, H)      # [d, gate, unit, k]
+    wf = torch.nn.functional.pad(w, (0, 4 * UT - H, 0, 4 * UT - H))
+    # lane = (k & 3) * 16 + (unit & 3) * 4 + gate
+    wf = wf.view(2, 4, UT, 4, UT, 4).permute(0, 2, 4, 5, 3, 1).reshape(2, UT, UT, 64).contiguous()
+    wb = torch.nn.functional.pad(w, (0, 16 * RT - H, 0, 4 * UT - H))
+    # lane = gate * 16 + (k & 15), k-step = unit
+    wb = wb.view(2, 4, 4 * UT, RT, 16).permute(0, 3, 2, 1, 4).reshape(2, RT, 4 * UT, 64).contiguous()
+    return wf, wb
+
+
+def _birnn_sizes(nseq, seq_len, H, who):
+    if nseq < 0 or seq_len < 1 or H < 1 or H > BIRNN_MAX_H:
+        raise L.HipError("%s: needs nseq >= 0, L >= 1 and 1 <= H <= %d (got %d, %d, %d)"
+                         % (who, BIRNN_MAX_H, nseq, seq_len, H))
+
+
+def _dense(t, shape, name):
+    if t is None or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise L.HipError("%s must be a contiguous %s tensor" % (name, tuple(shape)))
+
+
+def birnn_fwd(gx, whh_fwd, bhh, nseq, seq_len, H, gates, hprev, hlast, news, tok=None):
+    """nr_birnn_fwd: gx [nseq*L, 8H] -> news [nseq, H] (and tok [nseq*L, H]); saves gates (flat,
+    birnn_gates_numel floats), hprev [2, nseq*L, ldh >= H] and hlast [2, nseq, H]."""
+    _birnn_sizes(nseq, seq_len, H, "birnn_fwd")
+    _f32(gx, whh_fwd, bhh, gates, hprev, hlast, news, tok)
+    T = nseq * seq_len
+    UT = (H + 3) // 4
+    _rows_ok(gx, T, 8 * H, "gx")
+    _dense(whh_fwd, (2, UT, UT, 64), "birnn_fwd: whh_fwd")
+    if bhh is not None:
+        _dense(bhh, (2, 4 * H), "birnn_fwd: bhh")
+    if gates.dim() != 1 or gates.numel() < birnn_gates_numel(nseq, seq_len, H):
+        raise L.HipError("birnn_fwd: gates needs %d floats (flat)" % birnn_gates_numel(nseq, seq_len, H))
+    if hprev.dim() != 3 or hprev.shape[0] != 2 or hprev.shape[1] != T or hprev.shape[2] < H or not hprev.is_contiguous():
+        raise L.HipError("birnn_fwd: hprev must be a contiguous [2, nseq*L, >=H] tensor")
+    _dense(hlast, (2, nseq, H), "birnn_fwd: hlast")
+    _rows_ok(news, nseq, H, "news")
+    _rows_ok(tok, T, H, "tok")
+    for t in (gx, whh_fwd, bhh, gates, hprev, hlast, news, tok):
+        if t is not None and t.data_ptr() % 4:
+            raise L.HipError("birnn_fwd: a buffer is not 4-byte aligned")
+    L.call("nr_birnn_fwd", L.ptr(gx), gx.stride(0), L.ptr(whh_fwd), L.ptr(bhh), nseq, seq_len, H, L.ptr(gates),
+           L.ptr(hprev), hprev.stride(1), L.ptr(hlast), L.ptr(news), news.stride(0), L.ptr(tok),
+           tok.stride(0) if tok is not None else 0, L.stream_ptr(gx))
+
+
+def birnn_bwd(whh_bwd, gates, nseq, seq_len, H, dg, dnews=None, dtok=None):
+    """nr_birnn_bwd: dnews [nseq, H] and / or dtok [nseq*L, H] -> dg [nseq*L, 8H] (every row written)."""
+    _birnn_sizes(nseq, seq_len, H, "birnn_bwd")
+    _f32(whh_bwd, gates, dg, dnews, dtok)
+    T = nseq * seq_len
+    UT, RT = (H + 3) // 4, (H + 15) // 16
+    _dense(whh_bwd, (2, RT, 4 * UT, 64), "birnn_bwd: whh_bwd")
+    if gates.dim() != 1 or gates.numel() < birnn_gates_numel(nseq, seq_len, H):
+        raise L.HipError("birnn_bwd: gates needs %d floats (flat)" % birnn_gates_numel(nseq, seq_len, H))
+    if dnews is None and dtok is None:
+        raise L.HipError("birnn_bwd: dnews or dtok must be given")
+    _rows_ok(dg, T, 8 * H, "dg")
+    _rows_ok(dnews, nseq, H, "dnews")
+    _rows_ok(dtok, T, H, "dtok")
+    L.call("nr_birnn_bwd", L.ptr(whh_bwd), L.ptr(gates), nseq, seq_len, H, L.ptr(dnews),
+           dnews.stride(0) if dnews is not None else 0, L.ptr(dtok), dtok.stride(0) if dtok is not None else 0,
+           L.ptr(dg), dg.stride(0), L.stream_ptr(dg))
+
+
 def score_fwd(cdd, user, B, C, H, mode, logits, cdd_idx=None):
     _f32(cdd, user, logits)
     _rows_ok(user, B, H, "user")
