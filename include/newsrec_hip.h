@@ -955,6 +955,40 @@ int nr_bert_attn_bwd(const float* qkv, int64_t ldq, int64_t koff, int64_t voff, 
                      const float* ml, const uint32_t* keep, const float* dctx, int64_t ldd, float* work,
                      float* dqkv, int64_t lddq, int32_t prec, hipStream_t stream);
 
+/* ------------------------------------------------ one-layer BERT news encoder (Transformer_Encoder)
+ * The self-attention core of models/Modules/OneLayerBert.py's BertSelfAttention: ONE head as wide as
+ * the model, XSoftmax with the key-only mask, dropout on the probabilities.  For nseq titles of L
+ * tokens, with q / k / v at columns 0, koff, voff of qkv rows (ld ldq):
+ *   P[s][i][j]  = XSoftmax_j(scale * q_i . k_j, mask[s][j])   masked keys exactly 0; a title with no
+ *                 token gives all-zero rows (not uniform ones); padding queries attend like any other
+ *   ctx[s*L+i]  = sum_j (P[s][i][j] * keep / (1 - p_drop)) v_j          [nseq*L][D], ld ldc
+ *   probs       = P, [nseq][L][L]: after the mask, before the dropout
+ * Dropout: key = nr_dropout_key(seed, offset) (or of the device pair rng with offset added), element
+ * index (s * L + i) * L + j (mod 2^32).  mask: [nseq, L] of enum nr_mask_dtype.
+ * One workgroup per title, D walked in chunks of 64 columns through LDS; exact-f32 VALU fma chains,
+ * fp32 softmax; no atomics, two calls give the same bits.
+ * 1 <= L <= 64, 4 <= D <= 1024, D % 4 == 0; koff, voff multiples of 4 with koff >= D and
+ * voff >= koff + D; qkv, ctx (and dctx, dqkv below) 16-B aligned with ld % 4 == 0 and ld >= their
+ * width (voff + D for qkv / dqkv, D for ctx / dctx); 0 <= p_drop < 1.
+ * Errors (before any HIP call): -1000 a size, offset, ld, p_drop or mask_dtype outside the above,
+ * nseq < 0 or > 2^31 - 1, or a misaligned matrix; -1001 qkv, mask, probs or ctx NULL.  nseq == 0
+ * returns 0 without a launch. */
+int nr_sha_attn_fwd(const float* qkv, int64_t ldq, int64_t koff, int64_t voff, const void* mask,
+                    int32_t mask_dtype, int64_t nseq, int32_t L, int32_t D, float scale, float p_drop,
+                    uint64_t seed, uint64_t offset, const uint64_t* rng, float* ctx, int64_t ldc,
+                    float* probs, hipStream_t stream);
+
+/* Backward of nr_sha_attn_fwd from its saved probs and the same RNG triple, given dctx [nseq*L][D]
+ * (ld ldd).  With Pd = P * keep / (1 - p), dPd = dctx v^T and g = dPd * keep / (1 - p):
+ *   dV = Pd^T dctx,  dS = P * (g - rowsum(g * P)),  dQ = scale * dS k,  dK = scale * dS^T q
+ * written into dqkv (ld lddq) at the columns of qkv.  Every element of the three [nseq*L][D] blocks
+ * is stored, zeros included; columns outside them are left alone.  No atomics.
+ * Errors: as the forward, with dctx and dqkv for ctx (-1001 when NULL). */
+int nr_sha_attn_bwd(const float* qkv, int64_t ldq, int64_t koff, int64_t voff, const void* mask,
+                    int32_t mask_dtype, int64_t nseq, int32_t L, int32_t D, float scale, float p_drop,
+                    uint64_t seed, uint64_t offset, const uint64_t* rng, const float* probs,
+                    const float* dctx, int64_t ldd, float* dqkv, int64_t lddq, hipStream_t stream);
+
 /* dx = dy * (1 - y^2): the pooler's tanh backward (BertPooler). */
 int nr_tanh_bwd(const float* y, int64_t ldy, const float* dy, int64_t lddy, int64_t rows, int32_t cols,
                 float* dx, int64_t lddx, hipStream_t stream);

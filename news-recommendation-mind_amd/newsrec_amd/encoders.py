@@ -15,7 +15,8 @@ from torch import nn
 from . import _lib as L
 from .attention import MultiheadAttention
 from . import functions as F
-from .functions import AttnPoolFn, CNNNewsFn, CNNNewsRowsFn, MHAFn, MHANewsFn, RNNNewsFn, RNNUserFn
+from .functions import (AttnPoolFn, CNNNewsFn, CNNNewsRowsFn, MHAFn, MHANewsFn, RNNNewsFn, RNNUserFn,
+                        TransformerNewsFn)
 
 # fast eval: the MHA user encoder and its pooling in one launch (nr_mha_user_pool_fwd); False runs the
 # attention core and the pooling as two launches (the form the parity tests compare it with)
@@ -174,6 +175,114 @@ class RNN_Encoder(nn.Module):
                                     r.bias_ih_l0_reverse, r.bias_hh_l0_reverse, seq_len, pad_row, want_tokens)
         tok = tok.reshape(*lead, seq_len, self.hidden_dim) if tok is not None else None
         return tok, news.reshape(*lead, self.hidden_dim)
+
+    def forward(self, news_embedding, attn_mask=None):
+        L.require_gpu(news_embedding)
+        lead = news_embedding.shape[:-2]
+        seq_len, e = news_embedding.shape[-2:]
+        rows = news_embedding.reshape(-1, e).contiguous()
+        return self.encode_tokens(rows, _identity_rows(rows.shape[0], rows.device).view(*lead, seq_len),
+                                  attn_mask, pad_row=-1, want_tokens=True)
+
+
+class _BertSelfAttention(nn.Module):
+    def __init__(self, H, p):
+        super().__init__()
+        self.all_head_size = H
+        self.query = nn.Linear(H, H)
+        self.key = nn.Linear(H, H)
+        self.value = nn.Linear(H, H)
+        self.dropout = nn.Dropout(p)
+
+
+class _BertDenseLN(nn.Module):
+    """BertSelfOutput / BertOutput: dense, dropout, LayerNorm(+ residual)."""
+
+    def __init__(self, n_in, H, p, eps):
+        super().__init__()
+        self.dense = nn.Linear(n_in, H)
+        self.LayerNorm = nn.LayerNorm(H, eps=eps)
+        self.dropout = nn.Dropout(p)
+
+
+class _BertAttention(nn.Module):
+    def __init__(self, H, p_attn, p_hidden, eps):
+        super().__init__()
+        self.self = _BertSelfAttention(H, p_attn)
+        self.output = _BertDenseLN(H, H, p_hidden, eps)
+
+
+class _BertIntermediate(nn.Module):
+    def __init__(self, H):
+        super().__init__()
+        self.dense = nn.Linear(H, 4 * H)
+
+
+class _OneLayerBert(nn.Module):
+    """The parameter tree of models/Modules/OneLayerBert.py's BertLayer (its arithmetic is
+    functions.TransformerNewsFn)."""
+
+    def __init__(self, H, p_attn=0.1, p_hidden=0.1, eps=F.BERT_LN_EPS):
+        super().__init__()
+        self.attention = _BertAttention(H, p_attn, p_hidden, eps)
+        self.intermediate = _BertIntermediate(H)
+        self.output = _BertDenseLN(4 * H, H, p_hidden, eps)
+
+
+class Transformer_Encoder(nn.Module):
+    """models/Encoders/Transformer.py: project (Linear bert_dim -> H), one BERT layer with ONE attention
+    head as wide as the model (models/Modules/OneLayerBert.py: XSoftmax with the key mask, so a title
+    without a token attends to nothing; scale 1/sqrt(H)), then learned-query pooling over the layer's
+    output tokens (no tanh key; the reference's self.Tanh is unused).  The dropout rates (0.1, 0.1, 0.1)
+    and the LayerNorm eps (1e-12) are BertConfig()'s defaults, not manager.dropout_p; the three
+    nn.Dropout modules sit at the reference's attribute paths and their ``p`` is read at every forward.
+    hidden_dim must be a multiple of 4 and at most 1024 (nr_bert_add_ln_*'s float4 rows), so the
+    reference's default 150 is refused; titles of at most 64 tokens (nr_sha_attn_*, nr_seq_pool_*)."""
+
+    MAX_HIDDEN = 1024
+
+    def __init__(self, manager):
+        super().__init__()
+        self.hidden_dim = manager.hidden_dim
+        self.embedding_dim = manager.bert_dim     # the reference hard-codes BertConfig().hidden_size = 768
+        H = self.hidden_dim
+        if H % 4 or not 4 <= H <= self.MAX_HIDDEN:
+            raise ValueError("Transformer_Encoder: hidden_dim must be a multiple of 4 in [4, %d] "
+                             "(the add + LayerNorm kernels' float4 rows), got %d" % (self.MAX_HIDDEN, H))
+        self.project = nn.Linear(self.embedding_dim, H)
+        self.bert = _OneLayerBert(H)
+        self.query_words = nn.Parameter(torch.randn((1, H)))
+        self.Tanh = nn.Tanh()
+        nn.init.xavier_normal_(self.query_words)
+        self._rng = _DropoutStream()
+
+    def _params(self):
+        b = self.bert
+        at, ao, bo = b.attention.self, b.attention.output, b.output
+        return (self.project.weight, self.project.bias, at.query.weight, at.query.bias, at.key.weight, at.key.bias,
+                at.value.weight, at.value.bias, ao.dense.weight, ao.dense.bias, ao.LayerNorm.weight, ao.LayerNorm.bias,
+                b.intermediate.dense.weight, b.intermediate.dense.bias, bo.dense.weight, bo.dense.bias,
+                bo.LayerNorm.weight, bo.LayerNorm.bias, self.query_words)
+
+    def encode_tokens(self, table, token_ids, attn_mask=None, pad_row=0, want_tokens=False):
+        lead = token_ids.shape[:-1]
+        seq_len = token_ids.shape[-1]
+        T = token_ids.numel()
+        H = self.hidden_dim
+        if attn_mask is None:
+            attn_mask = torch.ones(T, dtype=torch.uint8, device=table.device)
+        drop, rng = None, None
+        if self.training:
+            b = self.bert
+            ps = (float(b.attention.self.dropout.p), float(b.attention.output.dropout.p), float(b.output.dropout.p))
+            if max(ps) > 0:
+                # one counter range for the three sites: T*L attention probabilities, then T*H twice
+                seed, off, rng = self._rng.take(T * seq_len + 2 * T * H, table.device)
+                drop = ps + (seed, off)
+        news, tok = TransformerNewsFn.apply(table, token_ids.reshape(T), _mask_rows(attn_mask, T), seq_len, pad_row,
+                                            want_tokens, drop, rng, *self._params())
+        tok = tok.reshape(*lead, seq_len, H) if tok is not None else None
+        return tok, news.reshape(*lead, H)
 
     def forward(self, news_embedding, attn_mask=None):
         L.require_gpu(news_embedding)

@@ -1170,6 +1170,139 @@ class RNNNewsFn(_GradAwareFn):
                 db_cat[4 * H:], db_hh[4 * H:], None, None, None)
 
 
+# ---------------------------------------------------------------------- one-layer BERT news encoder
+
+BERT_LN_EPS = 1e-12   # BertConfig().layer_norm_eps
+
+
+class TransformerNewsFn(_GradAwareFn):
+    """Transformer_Encoder.forward (models/Encoders/Transformer.py, models/Modules/OneLayerBert.py) on
+    gathered token rows: the [T, H, E] projection (gather fused), ONE [T, 3H, H] GEMM for query / key /
+    value, the one-head attention core nr_sha_attn_fwd (XSoftmax with the key mask, dropout on the
+    probabilities; always f32), dense + add + LayerNorm, the [T, 4H, H] GEMM with the GELU epilogue,
+    the [T, H, 4H] GEMM + add + LayerNorm, and the learned-query pooling over the tokens themselves
+    (nr_seq_pool_fwd without a key).  ``params``: project w, b; query / key / value w, b;
+    attention.output dense w, b, LayerNorm w, b; intermediate dense w, b; output dense w, b,
+    LayerNorm w, b; query_words.  ``drop``: (p_attn, p_attn_out, p_out, seed, offset) with ``rng`` the
+    device snapshot of one counter range of T*L + 2*T*H (sites in that order), or None (eval).
+    Returns (news [n, H], tok [T, H] or None)."""
+
+    @staticmethod
+    def forward(ctx, table, ids, mask, seq_len, pad_row, want_tokens, drop, rng, *params):
+        # an unused token output must not cost a zero-filled gradient
+        ctx.set_materialize_grads(False)
+        ctx.prec = K.get_gemm_precision()
+        wp, bp, wq, bq, wk, bk, wv, bv, wo, bo, l1w, l1b, wi, bi, wo2, bo2, l2w, l2b, query = \
+            [p.detach() for p in params]
+        T = ids.numel()
+        n = T // seq_len
+        E = table.shape[1]
+        H = wp.shape[0]
+        dev = table.device
+
+        def site(k):
+            """The kernels' dropout arguments of site k (0 attention, 1 attention output, 2 output)."""
+            if drop is None or drop[k] <= 0.0:
+                return dict(p_drop=0.0)
+            rel = (0, T * seq_len, T * seq_len + T * H)[k]
+            if rng is not None:    # the kernels add rel to the snapshot's device offset
+                return dict(p_drop=drop[k], seed=drop[3], offset=rel, rng=rng)
+            return dict(p_drop=drop[k], seed=drop[3], offset=drop[4] + rel)
+
+        x0 = _empty(T, H, table)
+        K.gemm(T, H, E, K.operand(table, L.KCONTIG, rows=ids, mapping=L.ROWS_GATHER), K.operand(wp, L.KCONTIG), x0,
+               bias=bp)
+        wqkv = torch.cat([wq, wk, wv], 0)
+        qkv = _empty(T, 3 * H, table)
+        K.gemm(T, 3 * H, H, K.operand(x0, L.KCONTIG), K.operand(wqkv, L.KCONTIG), qkv, bias=torch.cat([bq, bk, bv], 0))
+        cx = _empty(T, H, table)
+        probs = torch.empty(T * seq_len, device=dev)
+        K.sha_attn_fwd(qkv, mask, n, seq_len, H, cx, probs, **site(0))
+        a = _empty(T, H, table)
+        K.gemm(T, H, H, K.operand(cx, L.KCONTIG), K.operand(wo, L.KCONTIG), a, bias=bo)
+        h1 = _empty(T, H, table)
+        st1 = torch.empty(T, 2, device=dev)
+        K.bert_add_ln_fwd(a, x0, l1w, l1b, BERT_LN_EPS, h1, st1, **site(1))
+        U = _empty(T, 4 * H, table)
+        G = _empty(T, 4 * H, table)
+        K.gemm(T, 4 * H, H, K.operand(h1, L.KCONTIG), K.operand(wi, L.KCONTIG), G, bias=bi,
+               epilogue=L.EPI_STORE_GELU, c_rows=K.operand(U, L.KCONTIG))
+        o = _empty(T, H, table)
+        K.gemm(T, H, 4 * H, K.operand(G, L.KCONTIG), K.operand(wo2, L.KCONTIG), o, bias=bo2)
+        h2 = _empty(T, H, table)
+        st2 = torch.empty(T, 2, device=dev)
+        K.bert_add_ln_fwd(o, h1, l2w, l2b, BERT_LN_EPS, h2, st2, **site(2))
+        news = _empty(n, H, table)
+        pprobs = torch.empty(T, device=dev)
+        K.seq_pool_fwd(h2, query, mask, n, seq_len, H, news, pprobs)
+        ctx.save_for_backward(table, ids, mask, wp, wqkv, wo, l1w, wi, wo2, l2w, query, x0, qkv, cx, probs, a, st1,
+                              h1, U, G, o, st2, h2, pprobs)
+        ctx.cfg = (seq_len, pad_row, H)
+        ctx.site = site
+        ctx.table_ref = table
+        return news, (h2 if want_tokens else None)
+
+    @staticmethod
+    @_gemm_backward
+    def backward(ctx, dnews, dtok):
+        (table, ids, mask, wp, wqkv, wo, l1w, wi, wo2, l2w, query, x0, qkv, cx, probs, a, st1, h1, U, G, o, st2, h2,
+         pprobs) = ctx.saved_tensors
+        _word_row_flags(ctx.table_ref, None, None)
+        seq_len, pad_row, H = ctx.cfg
+        site = ctx.site
+        T = ids.numel()
+        n = T // seq_len
+        V, E = table.shape
+        dev = table.device
+        if dnews is None and dtok is None:
+            return (None,) * 27
+        if dnews is None:
+            dnews = torch.zeros(n, H, device=dev)
+        elif dnews.stride(-1) != 1:
+            dnews = dnews.contiguous()
+        if dtok is not None and (dtok.stride(-1) != 1 or dtok.stride(0) % 4 or dtok.data_ptr() % 16):
+            dtok = dtok.contiguous()
+        (dwp, dbp, dwqkv, dbqkv, dwo, dbo, dl1w, dl1b, dwi, dbi, dwo2, dbo2, dl2w, dl2b, dq) = _zeros_views(
+            dev, (H, E), (H,), (3 * H, H), (3 * H,), (H, H), (H,), (H,), (H,), (4 * H, H), (4 * H,), (H, 4 * H), (H,),
+            (H,), (H,), (H,))
+        # pooling: dh2 = p dnews + ds q (+ dtok)
+        dh2 = _empty(T, H, table)
+        K.seq_pool_bwd(h2, query, mask, n, seq_len, H, pprobs, dnews, dh2, dq, dz=dtok)
+        # BertOutput, BertIntermediate
+        dh1 = _empty(T, H, table)
+        do = _empty(T, H, table)
+        K.bert_add_ln_bwd(o, h1, l2w, st2, dh2, dh1, do, dl2w, dl2b, **site(2))
+        dU = _empty(T, 4 * H, table)
+        K.gemm(T, 4 * H, H, K.operand(do, L.KCONTIG), K.operand(wo2, L.MNCONTIG), dU, epilogue=L.EPI_GELU_GRAD,
+               c_rows=K.operand(U, L.KCONTIG))
+        _proj_wgrad(do, K.operand(G, L.MNCONTIG), dwo2, dbo2, T)
+        K.gemm(T, H, 4 * H, K.operand(dU, L.KCONTIG), K.operand(wi, L.MNCONTIG), dh1, epilogue=L.EPI_ACCUM)
+        _proj_wgrad(dU, K.operand(h1, L.MNCONTIG), dwi, dbi, T)
+        # BertSelfOutput, the attention core, query / key / value
+        dx0 = _empty(T, H, table)
+        da = _empty(T, H, table)
+        K.bert_add_ln_bwd(a, x0, l1w, st1, dh1, dx0, da, dl1w, dl1b, **site(1))
+        dcx = _empty(T, H, table)
+        K.gemm(T, H, H, K.operand(da, L.KCONTIG), K.operand(wo, L.MNCONTIG), dcx)
+        _proj_wgrad(da, K.operand(cx, L.MNCONTIG), dwo, dbo, T)
+        dqkv = _empty(T, 3 * H, table)
+        K.sha_attn_bwd(qkv, mask, n, seq_len, H, probs, dcx, dqkv, **site(0))
+        K.gemm(T, H, 3 * H, K.operand(dqkv, L.KCONTIG), K.operand(wqkv, L.MNCONTIG), dx0, epilogue=L.EPI_ACCUM)
+        _proj_wgrad(dqkv, K.operand(x0, L.MNCONTIG), dwqkv, dbqkv, T)
+        # the projection and the word table
+        _proj_wgrad(dx0, K.operand(table, L.MNCONTIG, rows=ids, mapping=L.ROWS_GATHER), dwp, dbp, T)
+        dtable = None
+        if ctx.needs_input_grad[0]:
+            dtable = table_grad_buffer(ctx.table_ref, V, E, dev, zero=True)
+            K.gemm(T, E, H, K.operand(dx0, L.KCONTIG), K.operand(wp, L.MNCONTIG), dtable, epilogue=L.EPI_SCATTER,
+                   c_rows=K.rows_map(ids, L.ROWS_GATHER), pad_row=pad_row)
+            if TABLE_GRAD_HOOK(ctx.table_ref, dtable):
+                dtable = None
+        return (dtable, None, None, None, None, None, None, None, dwp, dbp, dwqkv[:H], dbqkv[:H], dwqkv[H:2 * H],
+                dbqkv[H:2 * H], dwqkv[2 * H:], dbqkv[2 * H:], dwo, dbo, dl1w, dl1b, dwi, dbi, dwo2, dbo2, dl2w, dl2b,
+                dq.view_as(query))
+
+
 # ---------------------------------------------------------------------- scorer
 
 class ScoreFn(torch.autograd.Function):

@@ -1266,6 +1266,61 @@ def bert_attn_bwd(qkv, heads, mask, nseq, seq_len, ctx, ml, dctx, dqkv, koff=Non
            dqkv.stride(0), _prec(prec), L.stream_ptr(qkv))
 
 
+SHA_MAX_L = 64
+SHA_MAX_D = 1024
+
+
+def _sha_check(qkv, D, koff, voff, mask, nseq, seq_len, p_drop, who):
+    koff = D if koff is None else koff
+    voff = koff + D if voff is None else voff
+    if nseq < 0 or not 1 <= seq_len <= SHA_MAX_L or not 4 <= D <= SHA_MAX_D or D % 4:
+        raise L.HipError("%s: needs nseq >= 0, 1 <= L <= %d, 4 <= D <= %d and D %% 4 == 0 (got %d, %d, %d)"
+                         % (who, SHA_MAX_L, SHA_MAX_D, nseq, seq_len, D))
+    if koff % 4 or voff % 4 or koff < D or voff < koff + D:
+        raise L.HipError("%s: koff, voff must be multiples of 4 with koff >= D and voff >= koff + D" % who)
+    if not 0.0 <= p_drop < 1.0:
+        raise L.HipError("%s: 0 <= p_drop < 1 required" % who)
+    _f32(qkv)
+    _al(qkv, who + " qkv")
+    _rows_ok(qkv, nseq * seq_len, voff + D, "qkv")
+    mp, mdt = mask_arg(mask, nseq * seq_len)
+    return koff, voff, mp, mdt
+
+
+def sha_attn_fwd(qkv, mask, nseq, seq_len, D, ctx, probs, koff=None, voff=None, scale=None, p_drop=0.0, seed=0,
+                 offset=0, rng=None):
+    """nr_sha_attn_fwd: the one-head attention core of Transformer_Encoder on a fused [T, >= 3D]
+    (q | k | v) projection: ctx [T, D] and probs (flat, nseq*L*L floats: the softmax after the key
+    mask, before the dropout)."""
+    koff, voff, mp, mdt = _sha_check(qkv, D, koff, voff, mask, nseq, seq_len, p_drop, "sha_attn_fwd")
+    _f32(ctx, probs)
+    _al(ctx, "sha_attn_fwd ctx")
+    _rows_ok(ctx, nseq * seq_len, D, "ctx")
+    if not probs.is_contiguous() or probs.numel() < nseq * seq_len * seq_len:
+        raise L.HipError("sha_attn_fwd: probs needs nseq*L*L contiguous floats")
+    scale = 1.0 / float(D) ** 0.5 if scale is None else float(scale)
+    p, s, o, r = _drop(p_drop, seed, offset, rng)
+    L.call("nr_sha_attn_fwd", L.ptr(qkv), qkv.stride(0), koff, voff, mp, mdt, nseq, seq_len, D, scale, p, s, o, r,
+           L.ptr(ctx), ctx.stride(0), L.ptr(probs), L.stream_ptr(qkv))
+
+
+def sha_attn_bwd(qkv, mask, nseq, seq_len, D, probs, dctx, dqkv, koff=None, voff=None, scale=None, p_drop=0.0,
+                 seed=0, offset=0, rng=None):
+    """nr_sha_attn_bwd: dctx [T, D] -> dQ, dK, dV at qkv's columns of dqkv (every element stored)."""
+    koff, voff, mp, mdt = _sha_check(qkv, D, koff, voff, mask, nseq, seq_len, p_drop, "sha_attn_bwd")
+    _f32(probs, dctx, dqkv)
+    T = nseq * seq_len
+    for t, n, w in ((dctx, "dctx", D), (dqkv, "dqkv", voff + D)):
+        _al(t, "sha_attn_bwd " + n)
+        _rows_ok(t, T, w, n)
+    if not probs.is_contiguous() or probs.numel() < T * seq_len:
+        raise L.HipError("sha_attn_bwd: probs needs nseq*L*L contiguous floats")
+    scale = 1.0 / float(D) ** 0.5 if scale is None else float(scale)
+    p, s, o, r = _drop(p_drop, seed, offset, rng)
+    L.call("nr_sha_attn_bwd", L.ptr(qkv), qkv.stride(0), koff, voff, mp, mdt, nseq, seq_len, D, scale, p, s, o, r,
+           L.ptr(probs), L.ptr(dctx), dctx.stride(0), L.ptr(dqkv), dqkv.stride(0), L.stream_ptr(qkv))
+
+
 def tanh_bwd(y, dy, dx):
     _f32(y, dy, dx)
     rows, cols = y.shape

@@ -44,9 +44,10 @@ def build_model(encN, encU, hidden, vocab=30522, device="cuda", user_num=40, dro
     from .twotower import TwoTower
     m = cfg or ManagerConfig(encN, encU, hidden, device=device, dropout_p=dropout_p, user_num=user_num)
     emb = BERT_Embedding(m, vocab_size=vocab)
-    if encN not in ("cnn", "mha", "rnn"):
-        raise ValueError("unknown news encoder %r (cnn, mha or rnn)" % (encN,))
-    en = {"cnn": E.CNN_Encoder, "mha": E.MHA_Encoder, "rnn": E.RNN_Encoder}[encN](m)
+    if encN not in ("cnn", "mha", "rnn", "transformer"):
+        raise ValueError("unknown news encoder %r (cnn, mha, rnn or transformer)" % (encN,))
+    en = {"cnn": E.CNN_Encoder, "mha": E.MHA_Encoder, "rnn": E.RNN_Encoder,
+          "transformer": E.Transformer_Encoder}[encN](m)
     eu = {"attn": E.Attention_Pooling, "avg": E.Average_Pooling, "lstm": E.RNN_User_Encoder,
           "gru": E.RNN_User_Encoder, "lstur": E.LSTUR_User_Encoder, "mha": E.MHA_User_Encoder}[encU](m)
     model = TwoTower(m, emb, en, eu).to(device)
