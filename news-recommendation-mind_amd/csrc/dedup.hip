@@ -512,7 +512,7 @@ __device__ __forceinline__ void segsum_fix_body(const int bid, const int nblk, i
             drow[j] = s;
           }
           __syncthreads();
-        } else if (j < w4) {
+        } else if (g == 0 && j < w4) {   // 512 < w4 < 1024: the threads past the one group hold no sum
           drow[j] = s;
         }
       }

@@ -19,7 +19,9 @@ def _ids(T, V, seed, pad_frac=0.4):
     return ids
 
 
-# V <= 65536: count + fused scan (one launch); 200000: the multi-tile scan (two more launches)
+# every V takes the same three launches (count, scan over ceil(V / 4096) vocabulary tiles, fill): one tile
+# (5 .. 100), several (30522 .. 900000: tile totals collected in LDS, up to 256 tiles), and 1200000 (293
+# tiles: totals by global atomics)
 @pytest.mark.parametrize("T,V", [(1, 5), (37, 7), (1000, 30522), (52800, 30522), (4096, 100), (60000, 200000),
                                  (20000, 65536), (5000, 900000), (3000, 1200000)])
 def test_unique_rows(T, V):

@@ -39,8 +39,16 @@ def _with(base, **kw):
     return a
 
 
+def _show(v):
+    # a pointer into the buffer as "P" / "P+4": the address itself differs from run to run, and a test id
+    # must not
+    if isinstance(v, int) and not isinstance(v, bool) and 0 <= v - P < 4096:
+        return "P" if v == P else "P+%d" % (v - P)
+    return v
+
+
 def _label(kw):
-    return ", ".join("%s=%s" % (k, "P" if v is P else v) for k, v in kw.items())
+    return ", ".join("%s=%s" % (k, _show(v)) for k, v in kw.items())
 
 
 _W = dict(ldq=3 * 1028, koff=1028, voff=2056)
