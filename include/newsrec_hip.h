@@ -880,6 +880,76 @@ int nr_topk_news(const float* table, int64_t ldt, int64_t N, const float* user, 
                  float* top_scores, void* workspace, int64_t workspace_bytes, int32_t* status,
                  hipStream_t stream);
 
+/* ---------------------------------------------------------------- sparse (BM25) recall (csrc/bm25.hip)
+ * `--mode recall -rt s` (utils/Manager.py:52,117-119): the token-level inverted index of
+ * construct_inverted_index(corpus, BM25_token(corpus)) (utils/utils.py:219-246, :287-342), built on the
+ * device with the reference's quirks, a per-news view of it, and the exact top-K search over that view
+ * (the reference never ships the search).
+ *
+ * Corpus: tok int32 [R, L] (ld ldt), 1 <= L <= NR_BM25_MAX_L, R <= 2^31 - 1 rows, row 0 included.  V the
+ * vocabulary size, P the postings per token (<= NR_BM25_MAX_POSTINGS), k >= 1 BM25's integer k, special0..2
+ * the ids that never post (the reference's 0, 101, 102).
+ *   df[t]   occurrences of t in columns 1 .. L-1 of all rows (occurrences, not documents; pad and [SEP]
+ *           counted like any token)
+ *   tf[n][t] occurrences of t in columns 1 .. L-1 of row n
+ *   idf[t]  log((R - df + 0.5) / (df + 0.5) + 1) in fp64 where df[t] > 0, else 0.0 (negative when df > R).
+ *           Formed BY THE CALLER from df (host math.log: the reference's bits) and passed to nr_bm25_build.
+ *   posting row n posts token t when t occurs anywhere in row n (column 0 included) and t is not special:
+ *           s(t, n) = ((idf[t] * tf) * (k + 1)) / (tf + k), fp64, in that order (tf = 0 gives +-0.0)
+ *   list    token t's postings by s descending, equal s by ascending n, cut to P; post_ids int32 [V, P]
+ *           padded with R, post_scores fp64 [V, P] padded with +0.0
+ * A token outside [0, V) ORs NR_BM25_BAD_TOKEN into *status (caller zeroes) and is ignored.
+ *
+ * nr_bm25_count: df int64 [V] and n_post int32 [V] (the postings of each token before the cut); both
+ *   are zeroed by the call.  Integer atomics: exact.
+ * nr_bm25_build: post_ids / post_scores from tok, idf and nr_bm25_count's n_post.  workspace:
+ *   nr_bm25_build_workspace(R, L, V) bytes, 8-byte aligned.  Every element of both outputs is stored.
+ * nr_bm25_forward: the pruned index seen from the news side, aligned with tok.  Bit l of keep[n] (uint64
+ *   [R]) is set exactly when tok[n][l] is non-special and in range, column l is its first occurrence in
+ *   row n, and n is among the token's P postings; fwd[n][l] (fp32 [R, L], ld ldf) is then that posting's
+ *   score rounded once to fp32, and 0 elsewhere.  Both are fully written (zeroed, then scattered).
+ * Errors, nothing launched: 0 a size outside the above (or k < 1), 1 a null required pointer, 2 P outside
+ * [1, NR_BM25_MAX_POSTINGS], 4 a leading dimension below L, 6 workspace missing, misaligned or too small,
+ * 7 a kernel's launch bound or LDS limit is below what the launch needs. */
+#define NR_BM25_MAX_L 64
+#define NR_BM25_MAX_POSTINGS 1024
+enum nr_bm25_flags { NR_BM25_BAD_TOKEN = 1 };
+int nr_bm25_count(const int32_t* tok, int64_t ldt, int64_t R, int32_t L, int32_t V, int32_t special0,
+                  int32_t special1, int32_t special2, int64_t* df, int32_t* n_post, int32_t* status,
+                  hipStream_t stream);
+/* bytes of workspace nr_bm25_build needs; 0 on bad arguments */
+int64_t nr_bm25_build_workspace(int64_t R, int32_t L, int32_t V);
+int nr_bm25_build(const int32_t* tok, int64_t ldt, int64_t R, int32_t L, int32_t V, int32_t P, int32_t k,
+                  int32_t special0, int32_t special1, int32_t special2, const double* idf,
+                  const int32_t* n_post, int32_t* post_ids, double* post_scores, void* workspace,
+                  int64_t workspace_bytes, hipStream_t stream);
+int nr_bm25_forward(const int32_t* tok, int64_t ldt, int64_t R, int32_t L, int32_t V, int32_t P,
+                    const int32_t* post_ids, const double* post_scores, float* fwd, int64_t ldf,
+                    uint64_t* keep, hipStream_t stream);
+
+/* Sparse top-K.  qtok int32 [U, Tq] (ld ldq): a bag of query tokens per user; Q(u) = its in-range
+ * non-special tokens (duplicates, specials and out-of-range values are harmless).
+ *   s[u][n] = the fp32 sum, from 0.f in ascending l, of fwd[n][l] over the kept columns l of row n (keep
+ *             bits below L) whose token is in Q(u)
+ * Row n is eligible for u when at least one kept column matched (whatever the sign of the sum),
+ * n >= first_row, row_mask[n] != 0 and n is not among exclude[u] -- first_row, row_mask (uint8 [R]),
+ * exclude (int64 [U, E]), K, the output order (score descending, then id ascending), the -1 / -inf tail,
+ * n_slices and the workspace rule are those of nr_topk_news, with nr_bm25_topk_workspace(U, R, K, n_slices)
+ * bytes and 16 users x 64 news per workgroup tile.  A pure function of the inputs: no float atomics, the
+ * same bits for every n_slices.  The users' token bitmaps live in LDS (V bits per user, 16 users): a V
+ * whose bitmaps, with the buffers, exceed 160 KB is error 7.
+ * Errors, nothing launched: 0 a negative size, L outside [1, NR_BM25_MAX_L] or V < 1, 1 a null required
+ * pointer, 2 K outside [1, NR_TOPK_MAX_K], 3 E above NR_TOPK_MAX_EXCLUDE, 4 ldt or ldf below L or ldq
+ * below Tq, 5 n_slices above 64, 6 workspace missing or too small, 7 the launch bound or the LDS limit.
+ * U == 0 returns 0 and launches nothing. */
+int64_t nr_bm25_topk_workspace(int64_t U, int64_t R, int32_t K, int32_t n_slices);
+int nr_bm25_topk(const int32_t* qtok, int64_t ldq, int64_t U, int32_t Tq, const int32_t* tok, int64_t ldt,
+                 const float* fwd, int64_t ldf, const uint64_t* keep, int64_t R, int32_t L, int32_t V,
+                 int32_t special0, int32_t special1, int32_t special2, int32_t K, int64_t first_row,
+                 const uint8_t* row_mask, const int64_t* exclude, int32_t E, int32_t n_slices,
+                 int64_t* top_ids, float* top_scores, void* workspace, int64_t workspace_bytes,
+                 hipStream_t stream);
+
 /* ---------------------------------------------------------------- BERT towers (XFormer / PLM)
  * transformers BertModel as models/XFormer.py:68,94 and models/PLM.py:102,121 call it (token
  * type ids never passed: every token takes token_type_embeddings row 0).  The dense layers are

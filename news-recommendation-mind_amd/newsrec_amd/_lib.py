@@ -152,6 +152,14 @@ _SIGS = {
     "nr_topk_workspace": [c_i64, c_i64, c_i32, c_i32],
     "nr_topk_news": [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i32, c_i32, c_i64, c_ptr, c_ptr, c_i32, c_i32, c_ptr,
                      c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
+    "nr_bm25_count": [c_ptr, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr],
+    "nr_bm25_build_workspace": [c_i64, c_i32, c_i32],
+    "nr_bm25_build": [c_ptr, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr,
+                      c_ptr, c_i64, c_ptr],
+    "nr_bm25_forward": [c_ptr, c_i64, c_i64, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
+    "nr_bm25_topk_workspace": [c_i64, c_i64, c_i32, c_i32],
+    "nr_bm25_topk": [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32,
+                     c_i32, c_i32, c_i64, c_ptr, c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_i64, c_ptr],
     "nr_bert_embed_fwd": [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_f32,
                           c_f32, c_u64, c_u64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
     "nr_bert_embed_bwd": [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_f32, c_u64, c_u64,
@@ -184,7 +192,8 @@ _SIGS = {
 _RESTYPES = {"nr_segment_rows_sum_workspace": c_i64, "nr_bert_attn_keep_words": c_i64, "nr_unique_rows_workspace": c_i64, "nr_bert_attn_bwd_workspace": c_i64,
              "nr_colsum_workspace": c_i64, "nr_score_nll_workspace": c_i64,
              "nr_gemm_splitk_workspace": c_i64, "nr_cnn_keypool_workspace": c_i64,
-             "nr_topk_workspace": c_i64, "nr_grad_norm_workspace": c_i64, "nr_build_hash": ctypes.c_char_p}
+             "nr_topk_workspace": c_i64, "nr_grad_norm_workspace": c_i64, "nr_build_hash": ctypes.c_char_p,
+             "nr_bm25_build_workspace": c_i64, "nr_bm25_topk_workspace": c_i64}
 
 # enum nr_batch_flags / nr_metric_flags / nr_rank_flags, NR_RANK_MAX_GROUP
 BATCH_REVERSE_HISTORY, BATCH_SHUFFLE_POS, BATCH_CURSOR = 1, 2, 4
@@ -195,6 +204,10 @@ RANK_MAX_GROUP = 16384
 TOPK_NONFINITE = 1
 TOPK_MAX_K = 128
 TOPK_MAX_EXCLUDE = 256
+# enum nr_bm25_flags, NR_BM25_MAX_L, NR_BM25_MAX_POSTINGS
+BM25_BAD_TOKEN = 1
+BM25_MAX_L = 64
+BM25_MAX_POSTINGS = 1024
 
 _lib = None
 

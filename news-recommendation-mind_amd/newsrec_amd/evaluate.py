@@ -19,6 +19,11 @@ lists with all_gather_object.  Here:
                       then prediction.txt with the per-impression ordinal ranks and the text of
                       every line formed on the device (nr_rank_ordinal, nr_format_prediction)
                       and copied to the file in bounded slabs
+  topk_news / recommend / recall_metrics   dense recall (--mode recall -rt d): the K best rows of the
+                      whole encoded table per user (nr_topk_news) and recall@k / hit@k
+  build_bm25_index / sparse_topk_news / merge_recall   sparse recall (-rt s, sd): the reference's
+                      token-level BM25 inverted index (utils.py:219-246, :287-342) built on the device
+                      and the exact top-K search over it (nr_bm25_*); recommend(recall_type=...)
 
 history_from_table: the reference re-encodes each impression's history titles inside
 predict_fast (TwoTowerBaseModel.py:78-83 calls encode_user).  In eval mode the encoder is
@@ -442,9 +447,169 @@ def topk_news(table, user, k, first_row=1, row_mask=None, exclude=None, n_slices
     return ids, scores
 
 
+# ---------------------------------------------------------------- sparse recall (--mode recall -rt s)
+class BM25Index:
+    """The token-level BM25 inverted index of a corpus (csrc/bm25.hip; the definition is in
+    include/newsrec_hip.h), as build_bm25_index makes it:
+
+      tok          int32 [R, L]   the corpus (a store's tok: row 0 included)
+      post_ids     int32 [V, P]   token -> its P best rows, best first, padded with R
+      post_scores  fp64  [V, P]   their BM25 scores, padded with +0.0
+      df           int64 [V]      occurrences in columns 1 .. L-1;  idf fp64 [V] (formed on the host)
+      fwd, keep    fp32 [R, L], int64 [R] (a bit per column)   the pruned index seen from the news side
+      n_rows = R, vocab = V, postings = P, k, special; bad_tokens: a token outside [0, V) was ignored
+    """
+
+    def __init__(self, tok, post_ids, post_scores, df, idf, fwd, keep, k, special, bad_tokens=False):
+        self.tok, self.post_ids, self.post_scores, self.df, self.idf = tok, post_ids, post_scores, df, idf
+        self.fwd, self.keep, self.k, self.special = fwd, keep, int(k), tuple(int(s) for s in special)
+        self.n_rows, self.vocab, self.postings = tok.shape[0], post_ids.shape[0], post_ids.shape[1]
+        self.bad_tokens = bool(bad_tokens)
+
+    def to_reference(self):
+        """The [V, P, 2] float64 CPU tensor of (row, score) pairs that the reference saves as
+        inverted_index_bm25.pt (utils.py:234-245)."""
+        out = torch.empty(self.vocab, self.postings, 2, dtype=torch.float64)
+        out[:, :, 0] = self.post_ids.cpu().to(torch.float64)
+        out[:, :, 1] = self.post_scores.cpu()
+        return out
+
+    _ARRAYS = ("tok", "post_ids", "post_scores", "df", "idf", "fwd", "keep")
+
+    def save(self, path):
+        """np.savez of the arrays and parameters (no pickle).  -> the file written (.npz appended if absent)."""
+        path = path if path.endswith(".npz") else path + ".npz"
+        arrays = {n: getattr(self, n).cpu().numpy() for n in self._ARRAYS}
+        meta = np.array([self.k, int(self.bad_tokens)] + list(self.special), np.int64)
+        np.savez(path, meta=meta, **arrays)
+        return path
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        with np.load(path, allow_pickle=False) as z:
+            arrays = [torch.from_numpy(z[n]).to(device) for n in cls._ARRAYS]
+            meta = [int(v) for v in z["meta"]]
+        return cls(*arrays, k=meta[0], special=meta[2:5], bad_tokens=meta[1])
+
+
+def _check_tokens(t, name, who):
+    if t.dtype != torch.int32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(-1) != 1):
+        raise L.HipError("%s: %s must be a row-major 2-D int32 CUDA tensor" % (who, name))
+
+
+def build_bm25_index(tok, vocab=30522, postings=100, k=2, special=(0, 101, 102)):
+    """construct_inverted_index(corpus, BM25_token(corpus)) (utils.py:219-246, :287-342) of the corpus
+    ``tok`` int32 [R, L] (a store's tok) on the device -> BM25Index.  One small device-to-host copy: the
+    idf is formed on the host from the V occurrence counts with math.log, which makes it the reference's
+    bit for bit."""
+    import math
+    L.require_gpu(tok)
+    _check_tokens(tok, "tok", "build_bm25_index")
+    R, Ls = tok.shape
+    vocab, postings, k = int(vocab), int(postings), int(k)
+    special = tuple(int(s) for s in special)
+    if not 1 <= Ls <= L.BM25_MAX_L:
+        raise L.HipError("build_bm25_index: %d columns, at most %d" % (Ls, L.BM25_MAX_L))
+    if not 1 <= postings <= L.BM25_MAX_POSTINGS:
+        raise L.HipError("build_bm25_index: postings = %d outside [1, %d]" % (postings, L.BM25_MAX_POSTINGS))
+    if vocab < 1 or k < 1 or len(special) != 3:
+        raise L.HipError("build_bm25_index: vocab and k must be positive and special hold three ids")
+    dev = tok.device
+    df = torch.empty(vocab, dtype=torch.int64, device=dev)
+    n_post = torch.empty(vocab, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    S = L.stream_ptr(tok)
+    L.call("nr_bm25_count", L.ptr(tok), tok.stride(0), R, Ls, vocab, *special, L.ptr(df), L.ptr(n_post), L.ptr(status),
+           S)
+    idf = torch.tensor([math.log((R - d + 0.5) / (d + 0.5) + 1) if d > 0 else 0.0 for d in df.cpu().tolist()],
+                       dtype=torch.float64).to(dev)
+    post_ids = torch.empty(vocab, postings, dtype=torch.int32, device=dev)
+    post_scores = torch.empty(vocab, postings, dtype=torch.float64, device=dev)
+    ws_bytes = int(L.load().nr_bm25_build_workspace(R, Ls, vocab))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=dev)
+    L.call("nr_bm25_build", L.ptr(tok), tok.stride(0), R, Ls, vocab, postings, k, *special, L.ptr(idf), L.ptr(n_post),
+           L.ptr(post_ids), L.ptr(post_scores), L.ptr(ws), ws_bytes, S)
+    fwd = torch.empty(R, Ls, dtype=torch.float32, device=dev)
+    keep = torch.empty(R, dtype=torch.int64, device=dev)
+    L.call("nr_bm25_forward", L.ptr(tok), tok.stride(0), R, Ls, vocab, postings, L.ptr(post_ids), L.ptr(post_scores),
+           L.ptr(fwd), Ls, L.ptr(keep), S)
+    bad = bool(int(status.item()) & L.BM25_BAD_TOKEN)
+    return BM25Index(tok, post_ids, post_scores, df, idf, fwd, keep, k, special, bad)
+
+
+def sparse_topk_news(index, query_tokens, k, first_row=1, row_mask=None, exclude=None, n_slices=0):
+    """The k best rows of a BM25Index for every row of ``query_tokens`` int32 [U, Tq] (a bag of tokens per
+    user; specials, out-of-range values and repeats are harmless), exact (csrc/bm25.hip): score = the fp32
+    sum, in column order, of the row's kept postings whose token the user holds; a row with no such
+    posting is not returned.  first_row, row_mask, exclude, the order, the -1 / -inf tail and n_slices as
+    topk_news.  -> (ids int64 [U, k], scores fp32 [U, k])."""
+    L.require_gpu(index.tok, query_tokens, row_mask, exclude)
+    _check_tokens(query_tokens, "query_tokens", "sparse_topk_news")
+    R, Ls = index.tok.shape
+    U, Tq = query_tokens.shape
+    dev = index.tok.device
+    if query_tokens.device != dev:
+        raise L.HipError("sparse_topk_news: index and query_tokens are on different devices")
+    k = int(k)
+    if not 1 <= k <= L.TOPK_MAX_K:
+        raise L.HipError("sparse_topk_news: k = %d outside [1, %d]" % (k, L.TOPK_MAX_K))
+    if row_mask is not None:
+        if row_mask.dtype != torch.uint8 or row_mask.dim() != 1 or row_mask.numel() != R:
+            raise L.HipError("sparse_topk_news: row_mask must be uint8 [%d]" % R)
+        row_mask = row_mask.contiguous()
+    E = 0
+    if exclude is not None:
+        if exclude.dtype != torch.int64 or exclude.dim() != 2 or exclude.shape[0] != U:
+            raise L.HipError("sparse_topk_news: exclude must be int64 [%d, E]" % U)
+        E = exclude.shape[1]
+        if E > L.TOPK_MAX_EXCLUDE:
+            raise L.HipError("sparse_topk_news: %d exclude ids per user, at most %d" % (E, L.TOPK_MAX_EXCLUDE))
+        exclude = exclude.contiguous() if E else None
+    ids = torch.empty(U, k, dtype=torch.int64, device=dev)
+    scores = torch.empty(U, k, dtype=torch.float32, device=dev)
+    if U == 0:
+        return ids, scores
+    ws_bytes = int(L.load().nr_bm25_topk_workspace(U, R, k, int(n_slices)))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=dev)
+    L.call("nr_bm25_topk", L.ptr(query_tokens), max(query_tokens.stride(0), Tq), U, Tq, L.ptr(index.tok),
+           index.tok.stride(0), L.ptr(index.fwd), index.fwd.stride(0), L.ptr(index.keep), R, Ls, index.vocab,
+           *index.special, k, int(first_row), L.ptr(row_mask), L.ptr(exclude), E, int(n_slices), L.ptr(ids),
+           L.ptr(scores), L.ptr(ws), ws_bytes, L.stream_ptr(index.tok))
+    return ids, scores
+
+
+def history_tokens(store, his_id, his_mask):
+    """The query of sparse recall: the tokens of every user's history, int32 [U, his_size * L] =
+    store.tok[his_id] with the masked history slots set to pad (0).  Plain torch."""
+    U = his_id.shape[0]
+    t = store.tok[his_id.reshape(U, -1).long()]
+    t = t * (his_mask.reshape(U, -1, 1) != 0).to(t.dtype)
+    return t.reshape(U, -1).contiguous()
+
+
+def merge_recall(ids_a, ids_b):
+    """The "sd" merge of two recall lists [U, Ka], [U, Kb] (best first, -1 = no entry): round robin
+    a0, b0, a1, b1, ..., dropping -1 entries and ids already taken, compacted to the front and padded
+    with -1.  -> int64 [U, Ka + Kb].  Plain torch on the inputs' device (CPU tensors work)."""
+    if ids_a.dim() != 2 or ids_b.dim() != 2 or ids_a.shape[0] != ids_b.shape[0]:
+        raise ValueError("merge_recall takes two [U, K] id tensors with the same U")
+    U, (ka, kb) = ids_a.shape[0], (ids_a.shape[1], ids_b.shape[1])
+    W = max(ka, kb)
+    wide = [torch.nn.functional.pad(t.to(torch.int64), (0, W - t.shape[1]), value=-1) for t in (ids_a, ids_b)]
+    x = torch.stack(wide, 2).reshape(U, 2 * W)
+    vals, idx = torch.sort(x, dim=1, stable=True)           # equal ids stay in round-robin order
+    later = torch.zeros_like(vals, dtype=torch.bool)
+    later[:, 1:] = vals[:, 1:] == vals[:, :-1]
+    dup = torch.zeros_like(later).scatter_(1, idx, later)
+    valid = (x >= 0) & ~dup
+    front = torch.sort((~valid).to(torch.int8), dim=1, stable=True).indices
+    return torch.where(valid, x, torch.full_like(x, -1)).gather(1, front)[:, :ka + kb]
+
+
 @torch.no_grad()
-def recommend(model, store, k=10, batch_impr=1024, candidates="impressed", exclude_history=True, news_table=None):
-    """Dense recall over a dev or test split: the k best news of the WHOLE table for every impression's
+def recommend(model, store, k=10, batch_impr=1024, candidates="impressed", exclude_history=True, news_table=None,
+              recall_type="d", bm25=None):
+    """Recall over a dev or test split: the k best news of the WHOLE table for every impression's
     user, one row per impression (not per chunk).  -> (ids int64 [n_impr, k], scores fp32 [n_impr, k]),
     n_impr = len(store.grp_off_host) - 1.
 
@@ -454,23 +619,36 @@ def recommend(model, store, k=10, batch_impr=1024, candidates="impressed", exclu
     store.cand_ids (the reference's news_set, construct_cddidx_for_recall, Manager.py:1089-1113), "all"
     every row except the padded row 0.  exclude_history: the impression's own history is not recommended.
     news_table: an encode_news_table result to reuse.  Single process: the impressions are not sharded
-    over ranks (no ``group`` argument)."""
+    over ranks (no ``group`` argument).
+
+    recall_type (the reference's -rt, Manager.py:52): "d" dense (topk_news over the encoded table), "s"
+    sparse (sparse_topk_news of the history's tokens over ``bm25``, a BM25Index of store.tok, built here
+    when None; the model is not used), "sd" both: merge_recall(sparse, dense) ids [n_impr, 2k], scores None."""
     if store.mode not in ("dev", "test"):
         raise ValueError("recommend needs a dev or test split, not %s" % store.mode)
     if candidates not in ("impressed", "all"):
         raise ValueError("candidates must be 'impressed' or 'all'")
-    was_training = model.training
-    model.eval()
-    table = news_table if news_table is not None else encode_news_table(model, store)
-    dev = table.device
+    if recall_type not in ("d", "s", "sd"):
+        raise ValueError("recall_type must be 'd', 's' or 'sd'")
+    dense, sparse = "d" in recall_type, "s" in recall_type
+    dev, n_rows = store.tok.device, store.tok.shape[0]
+    if dense:
+        was_training = model.training
+        model.eval()
+        table = news_table if news_table is not None else encode_news_table(model, store)
+        dev, n_rows = table.device, table.shape[0]
+    if sparse:
+        index = bm25 if bm25 is not None else build_bm25_index(store.tok)
+        if index.n_rows != store.tok.shape[0]:
+            raise ValueError("bm25 indexes %d rows, the store has %d" % (index.n_rows, store.tok.shape[0]))
     mask = None
     if candidates == "impressed":
-        mask = torch.zeros(table.shape[0], dtype=torch.uint8, device=dev)
+        mask = torch.zeros(n_rows, dtype=torch.uint8, device=dev)
         mask[store.cand_ids] = 1
     first = store.first_chunk_host
     n_impr = len(first)
-    ids = torch.empty(n_impr, k, dtype=torch.int64, device=dev)
-    scores = torch.empty(n_impr, k, dtype=torch.float32, device=dev)
+    out = {t: (torch.empty(n_impr, k, dtype=torch.int64, device=dev),
+               torch.empty(n_impr, k, dtype=torch.float32, device=dev)) for t in recall_type}
     cache = {}
     for c0 in range(0, len(store), batch_impr):
         b = min(batch_impr, len(store) - c0)
@@ -480,11 +658,19 @@ def recommend(model, store, k=10, batch_impr=1024, candidates="impressed", exclu
         x = store.eval_batch(c0, b)
         rows = torch.from_numpy(first[i0:i1] - c0).to(dev)
         sub = {key: x[key][rows] for key in ("impr_index", "user_id", "his_id", "his_mask")}
-        user = user_reprs(model, table, sub, True, cache)
         his = sub["his_id"].reshape(i1 - i0, -1) if exclude_history else None
-        ids[i0:i1], scores[i0:i1] = topk_news(table, user, k, first_row=1, row_mask=mask, exclude=his)
-    model.train(was_training)
-    return ids, scores
+        if dense:
+            user = user_reprs(model, table, sub, True, cache)
+            out["d"][0][i0:i1], out["d"][1][i0:i1] = topk_news(table, user, k, first_row=1, row_mask=mask, exclude=his)
+        if sparse:
+            query = history_tokens(store, sub["his_id"], sub["his_mask"])
+            out["s"][0][i0:i1], out["s"][1][i0:i1] = sparse_topk_news(index, query, k, first_row=1, row_mask=mask,
+                                                                      exclude=his)
+    if dense:
+        model.train(was_training)
+    if recall_type == "sd":
+        return merge_recall(out["s"][0], out["d"][0]), None
+    return out[recall_type]
 
 
 def recall_metrics(top_ids, store, ks=(5, 10)):
