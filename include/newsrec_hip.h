@@ -404,6 +404,14 @@ int nr_mha_pool_bwd(const float* y, int64_t ldy, const int64_t* yrows, const voi
                     int32_t ws_copies, const int32_t* seg_off, int64_t dyu_row0, int64_t dy_rows,
                     uint32_t* dsto, int32_t prec, hipStream_t stream);
 
+/* The title walk of the nr_mha_pool_* kernels on the current device, for tests that choose title counts
+ * around it (nothing on the product path calls it).  pass: 0 = nr_mha_pool_fwd, 1 = the fused backward,
+ * 2 = the split backward's per-head attention pass.  Returns the launch's grid.x cap -- a pass with a
+ * cap S launches min(nseq, S) workgroups per head group, workgroup b taking titles b, b + S, ... (S =
+ * the workgroups the device holds at once, from the runtime's occupancy of the kernel, shared among the
+ * head groups) -- or 0 for a pass that launches one workgroup per title; negative: invalid argument. */
+int nr_mha_pool_walk_workgroups(int32_t pass, int32_t heads, int32_t dk, int32_t dv, int32_t prec);
+
 /* ------------------------------------------------------------------ pooling */
 
 /* Learned-query attention pooling of nseq sequences of L <= 64 rows of D features:

@@ -124,8 +124,9 @@ __device__ __forceinline__ uint64_t token_bits(const MPArgs& g, int64_t seq) {
 
 // Loads this lane's half of key row c = lane & 31 for one head (see below for the order).
 template <int DK, int NP>
-__device__ __forceinline__ void load_krow(const MPArgs& g, int64_t seq, int head, float (&a)[DK / 2]) {
-  const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+__device__ __forceinline__ void load_krow(const MPArgs& g, int64_t seq, int head, float (&a)[DK / 2],
+                                          int lane = threadIdx.x & 63) {
+  const int c = lane & 31, h = lane >> 5;
   constexpr int HK = DK / 2;
   if constexpr (NP > 0) {
     // bf16 steps: a[8t + u] = K[c][16t + 8h + u] (step t's eight k-slots of this lane half)
@@ -158,8 +159,9 @@ __device__ __forceinline__ void load_krow(const MPArgs& g, int64_t seq, int head
 // Block kb (features 32 kb .. 32 kb + 31) of the wave's key rows into the transpose tile tw[row][33]
 // from the lanes' half-rows in load_krow's order (lane (c, h) holds row c; rows past L are zero there)
 template <int DK, int NP>
-__device__ __forceinline__ void stage_kblock(const float (&a)[DK / 2], int kb, float* tw) {
-  const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+__device__ __forceinline__ void stage_kblock(const float (&a)[DK / 2], int kb, float* tw,
+                                             int lane = threadIdx.x & 63) {
+  const int c = lane & 31, h = lane >> 5;
   if constexpr (NP > 0) {   // a[8t + u] = K[c][16t + 8h + u]: steps t = 2kb, 2kb + 1
 #pragma unroll
     for (int t = 2 * kb; t < 2 * kb + 2; ++t)
@@ -177,8 +179,8 @@ __device__ __forceinline__ void stage_kblock(const float (&a)[DK / 2], int kb, f
 // returns P in p[16] (C layout).
 template <int DK, int NP>
 __device__ __forceinline__ void head_probs_from(const MPArgs& g, uint64_t bits, const float (&a)[DK / 2],
-                                                float (&p)[16]) {
-  const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+                                                float (&p)[16], int lane = threadIdx.x & 63) {
+  const int c = lane & 31, h = lane >> 5;
   constexpr int HK = DK / 2;
   f32x16 S;
 #pragma unroll
@@ -494,25 +496,26 @@ struct DoSource {
 // stage_rows*): recompute P from the key rows, dV = Pᵀ dO, dPᵀ = V dOᵀ, dS (XSoftmax
 // backward), W = dS + dSᵀ (tied Q = K), dK = W K; dV / dK rows to dy, their column sums added
 // to cs[] (dbias: cs[vb] for the value columns, cs[DV/32 + kb] for the key columns).
-template <int DK, int DV, int NP>
-__device__ __forceinline__ void head_bwd(const MPArgs& g, int64_t seq, int head, uint64_t bits, float* tw,
-                                         const DoSource<DV>& dO, float (&cs)[DV / 32 + DK / 32],
-                                         const uint32_t* dsto) {
-  const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+//
+// head_bwd_from is everything after P: ka[] is the lane's key half-row (kept for dK = W K, staged
+// through tw, not re-loaded), p[] its row of P.  VPRE: vr[] already holds the lane's half of value row
+// c in load_vrow's order (the persistent head pass issues it with the key rows); otherwise the dPᵀ
+// phase loads it.  WALK (the persistent head pass, which has the walk's state in registers too): the
+// dPᵀ / dS phase runs before dVp and re-reads P from the tile; the phases are independent, every
+// product and sum is the same.
+template <int DK, int DV, int NP, bool VPRE, bool WALK>
+__device__ __forceinline__ void head_bwd_from(const MPArgs& g, int head, const float (&ka)[DK / 2],
+                                              const float (&vr)[DV / 2], const float (&p)[16], float* tw,
+                                              const DoSource<DV>& dO, float (&cs)[DV / 32 + DK / 32],
+                                              const uint32_t* dsto, int lane = threadIdx.x & 63) {
+  const int c = lane & 31, h = lane >> 5;
   const int nq = g.heads * DK;
-
-  float p[16];
-  float ka[DK / 2];   // this lane's key half-row, kept for dK = W K (staged through tw, not re-loaded)
-  load_krow<DK, NP>(g, seq, head, ka);
-  head_probs_from<DK, NP>(g, bits, ka, p);
-  // phase fences: keep each phase's loads inside it (hoisting them all to the top costs more
-  // registers than the latency they would hide; the split kernel runs 4 waves per SIMD)
-  __builtin_amdgcn_sched_barrier(0);
-  // dVp = Pᵀ dO first (P is live anyway): Pᵀ through the transpose tile
-  {
+  // P into the transpose tile: read back transposed for dVp = Pᵀ dO
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tw[c * 33 + crow(r, h)] = p[r];
-    wave_lds_fence();
+  for (int r = 0; r < 16; ++r) tw[c * 33 + crow(r, h)] = p[r];
+  wave_lds_fence();
+  // dVp = Pᵀ dO
+  auto dv_phase = [&]() {
     float pt[16];
 #pragma unroll
     for (int s = 0; s < 16; ++s) pt[s] = tw[crow(s, h) * 33 + c];
@@ -536,10 +539,10 @@ __device__ __forceinline__ void head_bwd(const MPArgs& g, int64_t seq, int head,
       cs[vb] += sum;
       __builtin_amdgcn_sched_barrier(0);
     }
-  }
-  // dPᵀ = V dOᵀ  (lane (c, h): V[c][k], dO[c][k] over the interleaved k order)
+  };
+  // dPᵀ = V dOᵀ  (lane (c, h): V[c][k], dO[c][k] over the interleaved k order), then dS
   float dsv[16];
-  {
+  auto ds_phase = [&]() {
     f32x16 dpt;
 #pragma unroll
     for (int r = 0; r < 16; ++r) dpt[r] = 0.f;
@@ -549,8 +552,13 @@ __device__ __forceinline__ void head_bwd(const MPArgs& g, int64_t seq, int head,
       const float* vrr = yrow(g, rv ? c : 0) + nq + head * DV + 4 * h;   // clamp, zero by select
 #pragma unroll
       for (int s = 0; s < HV; s += 4) {
-        float4 v4 = *reinterpret_cast<const float4*>(vrr + 2 * s);
-        if (!rv) v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 v4;
+        if constexpr (VPRE) {
+          v4 = make_float4(vr[s], vr[s + 1], vr[s + 2], vr[s + 3]);
+        } else {
+          v4 = *reinterpret_cast<const float4*>(vrr + 2 * s);
+          if (!rv) v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         const int col = 4 * h + 2 * s;
         dpt = __builtin_amdgcn_mfma_f32_32x32x2f32(v4.x, dO.at(c, col), dpt, 0, 0, 0);
         dpt = __builtin_amdgcn_mfma_f32_32x32x2f32(v4.y, dO.at(c, col + 1), dpt, 0, 0, 0);
@@ -562,23 +570,41 @@ __device__ __forceinline__ void head_bwd(const MPArgs& g, int64_t seq, int head,
 #pragma unroll
       for (int t = 0; t < DV / 16; ++t) {
         float va[8], oa[8];
+        if constexpr (VPRE) {
 #pragma unroll
-        for (int q4 = 0; q4 < 2; ++q4) {
-          const float4 v4 = *reinterpret_cast<const float4*>(vrr + 16 * t + 4 * q4);
-          va[4 * q4] = rv ? v4.x : 0.f; va[4 * q4 + 1] = rv ? v4.y : 0.f;
-          va[4 * q4 + 2] = rv ? v4.z : 0.f; va[4 * q4 + 3] = rv ? v4.w : 0.f;
+          for (int u = 0; u < 8; ++u) va[u] = vr[8 * t + u];
+        } else {
+#pragma unroll
+          for (int q4 = 0; q4 < 2; ++q4) {
+            const float4 v4 = *reinterpret_cast<const float4*>(vrr + 16 * t + 4 * q4);
+            va[4 * q4] = rv ? v4.x : 0.f; va[4 * q4 + 1] = rv ? v4.y : 0.f;
+            va[4 * q4 + 2] = rv ? v4.z : 0.f; va[4 * q4 + 3] = rv ? v4.w : 0.f;
+          }
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) oa[u] = dO.at(c, 16 * t + 8 * h + u);
         mfma_x<NP>(dpt, planes8<NP>(va), planes8<NP>(oa));
       }
     }
+    // WALK: the lane's row of P comes back from the tile (the words it wrote above), so P holds no
+    // registers through the phases between
+    float pr[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) pr[r] = WALK ? tw[c * 33 + crow(r, h)] : p[r];
     float rs = 0.f;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) rs = fmaf(p[r], dpt[r], rs);
+    for (int r = 0; r < 16; ++r) rs = fmaf(pr[r], dpt[r], rs);
     rs += __shfl_xor(rs, 32, 64);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) dsv[r] = p[r] * (dpt[r] - rs) * g.scale_attn;
+    for (int r = 0; r < 16; ++r) dsv[r] = pr[r] * (dpt[r] - rs) * g.scale_attn;
+  };
+  if constexpr (WALK) {   // the value rows (in registers since the title's top) are consumed first
+    ds_phase();
+    __builtin_amdgcn_sched_barrier(0);
+    dv_phase();
+  } else {                // P is live anyway: dVp first
+    dv_phase();
+    ds_phase();
   }
   __builtin_amdgcn_sched_barrier(0);
   // W = dS + dSᵀ via the per-wave transpose tile
@@ -591,7 +617,7 @@ __device__ __forceinline__ void head_bwd(const MPArgs& g, int64_t seq, int head,
   // dKp = W Kp  -> dY[:, head*DK ..]; K's 32-feature block kb from the lanes' key rows through tw
 #pragma unroll
   for (int kb = 0; kb < DK / 32; ++kb) {
-    stage_kblock<DK, NP>(ka, kb, tw);
+    stage_kblock<DK, NP>(ka, kb, tw, lane);
     wave_lds_fence();
     float bk[16];
 #pragma unroll
@@ -611,6 +637,21 @@ __device__ __forceinline__ void head_bwd(const MPArgs& g, int64_t seq, int head,
     cs[DV / 32 + kb] += sum;
     __builtin_amdgcn_sched_barrier(0);
   }
+}
+
+template <int DK, int DV, int NP>
+__device__ __forceinline__ void head_bwd(const MPArgs& g, int64_t seq, int head, uint64_t bits, float* tw,
+                                         const DoSource<DV>& dO, float (&cs)[DV / 32 + DK / 32],
+                                         const uint32_t* dsto) {
+  float p[16];
+  float ka[DK / 2];
+  load_krow<DK, NP>(g, seq, head, ka);
+  head_probs_from<DK, NP>(g, bits, ka, p);
+  // phase fences: keep each phase's loads inside it (hoisting them all to the top costs more
+  // registers than the latency they would hide)
+  __builtin_amdgcn_sched_barrier(0);
+  const float none[DV / 2] = {};
+  head_bwd_from<DK, DV, NP, false, false>(g, head, ka, none, p, tw, dO, cs, dsto);
 }
 
 // dbias column sums of one head: lanes of the two halves hold partial sums of the same column
@@ -813,41 +854,138 @@ __global__ __launch_bounds__(256) void mha_ln_bwd_kernel(MPArgs g) {
   }
 }
 
-// Split backward, kernel 2: attention backward, one wave per head, HB_TITLES titles per
-// workgroup in sequence (the dbias column sums accumulate in registers across them: one
-// atomic per column per workgroup instead of per title).  Each wave stages its title's
-// projection-row indices in a private slice of LDS.
-constexpr int HB_TITLES = 1;
+// Split backward, kernel 2: attention backward, one wave per head.  Persistent: grid.x is capped at
+// the workgroups resident per head group (head_walk_cap) and workgroup b walks titles b, b + gridDim.x,
+// ... -- a bounded loop, no workgroup waits for another.  The dbias column sums accumulate in
+// registers across the walk: one atomic per column per workgroup, not per title.
+//
+// A title's loads are one batch.  Its index data (projection-row offsets through yrows, dy row
+// offsets, mask bits) is fetched one title ahead: issued at the top of the previous title, parked in
+// the wave's staging slot once that title's dO slice is built, promoted to rows[] / dsts[] after the
+// fence that ends that title.  So the key half-rows, the O slice, the LN row terms and γ / q / dnews all
+// issue together at the title's top, the value half-rows once the dO slice is built (before the S
+// products, not inside the dPᵀ phase that reads them); only a workgroup's first title pays the index
+// round trip.  A prefetch past the last title re-reads the last one (clamped, no branch around a load).
+constexpr int HB_STAGE = 65;   // staging words per wave: [0,32) row offsets, [32,64) dy offsets, [64] mask bits
+
+struct HbIndex { uint32_t yr, ds, mb, m0, m1; };   // the words as loaded; hb_index_stage converts them
+
+// Every lane loads (lanes l and l + 32 the same words) and every address is valid whatever the
+// argument forms: an absent yrows / dsto and the mask widths that do not apply read y's first words
+// instead, dropped by a select.  Nothing is computed from the words here, so nothing waits for them.
+// Addresses are a uniform base + a 32-bit byte offset (the token count fits: its dy offsets do).
+__device__ __forceinline__ HbIndex hb_index_load(const MPArgs& g, int seq, int lane) {
+  const int l = lane & 31;
+  const uint32_t t = (uint32_t)(seq * g.L + (l < g.L ? l : 0));
+  const char* safe = reinterpret_cast<const char*>(g.y);
+  const auto word = [](const char* base, uint32_t off) { return *reinterpret_cast<const uint32_t*>(base + off); };
+  HbIndex ix;
+  // the low word of the row id: the byte offsets are formed modulo 2^32 (row_byte_off)
+  ix.yr = word(g.yrows ? reinterpret_cast<const char*>(g.yrows) : safe, g.yrows ? 8u * t : 0u);
+  ix.ds = word(g.dsto ? reinterpret_cast<const char*>(g.dsto) : safe, g.dsto ? 4u * t : 0u);
+  const uint32_t es = g.mask_dt == NR_MASK_U8 ? 1u : g.mask_dt == NR_MASK_F32 ? 4u : 8u;
+  const char* mask = reinterpret_cast<const char*>(g.mask);
+  ix.mb = *reinterpret_cast<const uint8_t*>(mask + es * t);
+  ix.m0 = word(es == 1 ? safe : mask, es == 1 ? 0u : es * t);
+  ix.m1 = word(es == 1 ? safe : mask, es == 1 ? 0u : es * t + (es == 8 ? 4u : 0u));
+  return ix;
+}
+
+// row_byte_off / dy offsets (~0: no write, as the one-title form had them) / token_bits of title seq
+// from hb_index_load's words, into the wave's staging slot
+__device__ __forceinline__ void hb_index_stage(const MPArgs& g, int seq, const HbIndex& ix, uint32_t* stg,
+                                               int lane) {
+  const int l = lane & 31;
+  const uint32_t t = (uint32_t)(seq * g.L + (l < g.L ? l : 0));
+  const uint32_t roff = (g.yrows ? ix.yr : t) * (uint32_t)(g.ldy * 4);
+  uint32_t doff = g.dsto ? ix.ds : t * (uint32_t)(g.lddy * 4);
+  if (l >= g.L) doff = ~0u;
+  stg[lane] = lane < 32 ? roff : doff;
+  const bool m = g.mask_dt == NR_MASK_U8    ? ix.mb != 0
+                 : g.mask_dt == NR_MASK_I64 ? (ix.m0 | ix.m1) != 0
+                 : g.mask_dt == NR_MASK_F64 ? (ix.m0 | (ix.m1 & 0x7fffffffu)) != 0   // != 0.0: -0.0 is zero
+                                            : (ix.m0 & 0x7fffffffu) != 0;
+  const uint64_t bits = __ballot(lane < g.L && m);
+  if (lane == 0) stg[64] = (uint32_t)bits;   // L <= 32
+}
+
+// The staged title becomes the current one; returns its mask bits.  Call after the fence that ends the
+// previous title (its reads of rows[] / dsts[] are done) and that published the staging slot.
+__device__ __forceinline__ uint64_t hb_index_promote(const uint32_t* stg, uint32_t* rows, uint32_t* dsts,
+                                                    int lane) {
+  const uint32_t v = stg[lane];
+  const uint32_t b = stg[64];
+  (lane < 32 ? rows : dsts - 32)[lane] = v;
+  wave_lds_fence();
+  return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+}
+
+// This lane's half of value row c = lane & 31 of one head in the k order of head_bwd_from's dPᵀ phase
+// (rows past L clamped and zeroed by a select, as load_krow)
+template <int DK, int DV, int NP>
+__device__ __forceinline__ void load_vrow(const MPArgs& g, int head, float (&vr)[DV / 2], int lane) {
+  const int c = lane & 31, h = lane >> 5;
+  const bool ok = c < g.L;
+  const float* vrr = yrow(g, ok ? c : 0) + g.heads * DK + head * DV;
+  if constexpr (NP == 0) {
+#pragma unroll
+    for (int s = 0; s < DV / 2; s += 4) {
+      const float4 v = *reinterpret_cast<const float4*>(vrr + 4 * h + 2 * s);
+      vr[s] = ok ? v.x : 0.f; vr[s + 1] = ok ? v.y : 0.f; vr[s + 2] = ok ? v.z : 0.f; vr[s + 3] = ok ? v.w : 0.f;
+    }
+  } else {
+#pragma unroll
+    for (int t = 0; t < DV / 16; ++t)
+#pragma unroll
+      for (int q4 = 0; q4 < 2; ++q4) {
+        const float4 v = *reinterpret_cast<const float4*>(vrr + 8 * h + 16 * t + 4 * q4);
+        float* d = vr + 8 * t + 4 * q4;
+        d[0] = ok ? v.x : 0.f; d[1] = ok ? v.y : 0.f; d[2] = ok ? v.z : 0.f; d[3] = ok ? v.w : 0.f;
+      }
+  }
+}
 
 template <int DK, int DV, int NP>
 __global__ __launch_bounds__(256, 4) void mha_head_bwd_kernel(MPArgs g) {
   if (g.rng) g.dkey = nr_dropout_key(g.rng[0], g.rng[1] + g.offset);   // graph-replay RNG (dO's dropout)
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  // the wave index as a scalar: the wave's LDS slices and its head are then addressed from SGPRs
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
   const int head = blockIdx.y * nw + w;
   if (head >= g.heads) return;   // no block-wide barrier below
   uint32_t* rows = reinterpret_cast<uint32_t*>(sm) + 32 * w;   // this wave's staged row offsets (yrow)
   uint32_t* dsts = reinterpret_cast<uint32_t*>(sm) + 32 * nw + 32 * w;   // ... and dy row offsets
   float* tw = sm + 64 * nw + w * 32 * 33;                     // this wave's transpose tile
   float* dot = sm + 64 * nw + nw * 32 * 33 + w * 32 * (DV + 1);   // this wave's dO slice [32][DV+1]
+  uint32_t* stg = reinterpret_cast<uint32_t*>(sm) + 64 * nw + nw * 32 * 33 + nw * 32 * (DV + 1) + HB_STAGE * w;
   float cs[DV / 32 + DK / 32];
 #pragma unroll
   for (int i = 0; i < DV / 32 + DK / 32; ++i) cs[i] = 0.f;
-  const int64_t s0 = (int64_t)blockIdx.x * HB_TITLES;
+  // titles as 32-bit ints (nseq * L rows of dy are addressed by 32-bit byte offsets): scalar compares
+  const int G = gridDim.x, nseq = (int)g.nseq;
+  int seq0 = blockIdx.x;   // < nseq: the launch caps grid.x at nseq
+  hb_index_stage(g, seq0, hb_index_load(g, seq0, threadIdx.x & 63), stg, threadIdx.x & 63);
+  wave_lds_fence();
 #pragma unroll 1
-  for (int64_t seq = s0; seq < s0 + HB_TITLES && seq < g.nseq; ++seq) {
-    // every global load of the prologue in flight together: row ids, mask, the head's dO slice
-    const uint32_t roff = lane < 32 ? row_byte_off(g, seq * g.L + (lane < g.L ? lane : 0)) : 0u;
-    const uint64_t bits = token_bits(g, seq);
-    uint32_t doff = ~0u;
-    if (lane < g.L) doff = g.dsto ? g.dsto[seq * g.L + lane] : (uint32_t)((seq * g.L + lane) * g.lddy * 4);
+  for (; seq0 < nseq; seq0 += G) {
+    const int64_t seq = seq0;
+    // The lane id is opaque per title: everything a title derives from it (addresses, column offsets,
+    // the dropout hash's column terms, mask shifts) is then formed inside the title, as the one-title
+    // kernel formed it once.  Hoisted out of the walk these loop invariants outnumber the registers
+    // and spill (measured at compile time: 356 bytes of scratch per lane instead of 0).
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
+    const int c = lane & 31, h = lane >> 5;
+    const uint64_t bits = hb_index_promote(stg, rows, dsts, lane);
+    const int nxt = seq0 + G < nseq ? seq0 + G : nseq - 1;
+    const HbIndex nix = hb_index_load(g, nxt, lane);
     constexpr int F4 = DV / 4;                 // float4 per dO row
     constexpr int PER = 32 * F4 / 64;          // per lane
     static_assert(64 % F4 == 0, "a lane keeps its four columns in every row it loads");
     // this head's slice of dO, rebuilt from the saved attention output O and the LN pass's row terms
     // (ln_row_dO: the dO rows never go through HBM); lane: rows e / F4 of e = lane + 64 i, columns
     // 4 (lane % F4) .. + 3 of the head
-    float4 v[PER], ra[PER], rb[PER];
+    float4 v[PER];
     const int col0 = head * DV + 4 * (lane % F4);
     {
       const float* src = g.o + (seq * g.L) * g.ldo + head * DV;
@@ -857,11 +995,11 @@ __global__ __launch_bounds__(256, 4) void mha_head_bwd_kernel(MPArgs g) {
         const int rr = r < g.L ? r : 0;
         v[i] = *reinterpret_cast<const float4*>(
             reinterpret_cast<const char*>(src) + 4u * (uint32_t)(rr * (int)g.ldo + 4 * c4));
-        const float4* rc = reinterpret_cast<const float4*>(g.dob + (seq * g.L + rr) * g.lddob);
-        ra[i] = rc[0];   // mean, rstd, sg, sgx
-        rb[i] = rc[1];   // ds_l, p_l
       }
     }
+    // the row terms once per row, not per element chunk: lane (c, h) loads half h of row c's eight
+    // (mean, rstd, sg, sgx | ds_l, p_l, -, -); the lanes pick their rows' terms up from tw below
+    const float4 rt = reinterpret_cast<const float4*>(g.dob + (seq * g.L + (c < g.L ? c : 0)) * g.lddob)[h];
     float gm[4], qd[4], dn[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -869,6 +1007,10 @@ __global__ __launch_bounds__(256, 4) void mha_head_bwd_kernel(MPArgs g) {
       qd[j] = g.q[col0 + j];
       dn[j] = g.news[seq * g.ldn + col0 + j];
     }
+    float ka[DK / 2], vr[DV / 2];
+    load_krow<DK, NP>(g, seq, head, ka, lane);
+    *reinterpret_cast<float4*>(tw + 8 * c + 4 * h) = rt;
+    wave_lds_fence();
     {
       const bool drop = g.p_drop > 0.f;
       const float dsc = drop ? 1.f / (1.f - g.p_drop) : 1.f;
@@ -876,23 +1018,21 @@ __global__ __launch_bounds__(256, 4) void mha_head_bwd_kernel(MPArgs g) {
 #pragma unroll
       for (int i = 0; i < PER; ++i) {
         const int r = (lane + 64 * i) / F4;
-        const int64_t row = seq * g.L + (r < g.L ? r : 0);
+        const int rr = r < g.L ? r : 0;
+        const int64_t row = seq * g.L + rr;
+        const float4 ra = *reinterpret_cast<const float4*>(tw + 8 * rr);       // mean, rstd, sg, sgx
+        const float2 rb = *reinterpret_cast<const float2*>(tw + 8 * rr + 4);   // ds_l, p_l
         float o[4] = {v[i].x, v[i].y, v[i].z, v[i].w}, d[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const uint32_t col = (uint32_t)(col0 + j);
           const bool keep = !drop || nr_dropout_keep(g.dkey, (uint32_t)row * Hc + col, g.dthresh);
           const float dzv = g.dz ? g.dz[row * g.lddz + col] : 0.f;
-          const float xh = (o[j] - ra[i].x) * ra[i].y;
-          d[j] = ln_row_dO(xh, ra[i].y, ra[i].z, ra[i].w, rb[i].y, rb[i].x, dn[j], qd[j], gm[j], dzv,
-                           keep ? dsc : 0.f);
+          const float xh = (o[j] - ra.x) * ra.y;
+          d[j] = ln_row_dO(xh, ra.y, ra.z, ra.w, rb.y, rb.x, dn[j], qd[j], gm[j], dzv, keep ? dsc : 0.f);
         }
         v[i] = r < g.L ? make_float4(d[0], d[1], d[2], d[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
-    }
-    if (lane < 32) {
-      rows[lane] = roff;
-      dsts[lane] = doff;
     }
 #pragma unroll
     for (int i = 0; i < PER; ++i) {   // dO slice into LDS, rows >= L zero
@@ -900,10 +1040,18 @@ __global__ __launch_bounds__(256, 4) void mha_head_bwd_kernel(MPArgs g) {
       float* d = dot + r * (DV + 1) + 4 * c4;
       d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; d[3] = v[i].w;
     }
+    hb_index_stage(g, nxt, nix, stg, lane);   // issued first of this title's loads: here long since
     wave_lds_fence();
     DoSource<DV> dO{dot, DV + 1, g.L, false};
-    head_bwd<DK, DV, NP>(g, seq, head, bits, tw, dO, cs, dsts);
-    wave_lds_fence();   // the next title's row indices / dO overwrite these
+    // the value rows go out here, behind the S products and the softmax (the dPᵀ phase, which reads
+    // them, follows P directly); issued with the key rows at the title's top they would hold 16 more
+    // registers through the dO slice's build and spill (52 bytes of scratch per lane at <64, 32, 0>)
+    load_vrow<DK, DV, NP>(g, head, vr, lane);
+    float p[16];
+    head_probs_from<DK, NP>(g, bits, ka, p, lane);
+    __builtin_amdgcn_sched_barrier(0);   // phase fence, as head_bwd
+    head_bwd_from<DK, DV, NP, true, true>(g, head, ka, vr, p, tw, dO, cs, dsts, lane);
+    wave_lds_fence();   // the next title's row indices / dO / row terms overwrite these
   }
   flush_dbias<DK, DV>(g, head, cs);
 }
@@ -934,9 +1082,35 @@ size_t bwd_smem(int H, int nw) {
   return (size_t)(32 + 32 * (H + 1) + 32 + 32 + 64 + 2 * 32 * (H / 64) + (tiles > red ? tiles : red)) * sizeof(float);
 }
 
-size_t head_bwd_smem(int nw, int dv) { return (size_t)(64 * nw + nw * 32 * 33 + nw * 32 * (dv + 1)) * sizeof(float); }
+size_t head_bwd_smem(int nw, int dv) {
+  return (size_t)(64 * nw + nw * 32 * 33 + nw * 32 * (dv + 1) + nw * HB_STAGE) * sizeof(float);
+}
 
 enum Pass { FWD = 0, BWD_FUSED = 1, BWD_SPLIT = 2 };
+
+// Workgroups of `kern` the device holds at once: CUs x the occupancy the runtime reports for the
+// block size and dynamic LDS the launch uses; asked once per device.
+template <typename Kern>
+int resident_workgroups(Kern kern, int threads, size_t smem) {
+  static int cache[16] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+  if (cache[dev] == 0) {
+    int cus = 0, per = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, threads, smem) != hipSuccess || per < 1) per = 1;
+    cache[dev] = cus * per;
+  }
+  return cache[dev];
+}
+
+// grid.x cap of the persistent head pass: the resident workgroups shared among the gy head groups
+template <int DK, int DV, int NP>
+int head_walk_cap(int heads) {
+  const int gy = (heads + 3) / 4;
+  const int n = resident_workgroups(mha_head_bwd_kernel<DK, DV, NP>, 256, head_bwd_smem(4, DV)) / gy;
+  return n < 1 ? 1 : n;
+}
 
 template <typename K>
 void allow_smem(K kern, size_t sz) {
@@ -1135,9 +1309,15 @@ int launch_user_pool(const MPArgs& g, hipStream_t s) {
   return NR_OK;
 }
 
+// walk (nr_mha_pool_walk_workgroups): nothing is launched, *walk receives the pass's grid.x cap (0: the
+// pass launches one workgroup per title)
 template <int DK, int DV, int NH64, int NP>
-int launch_np(const MPArgs& g, Pass pass, hipStream_t s) {
+int launch_np(const MPArgs& g, Pass pass, hipStream_t s, int* walk) {
   const int H = NH64 * 64;
+  if (walk) {
+    *walk = pass == BWD_SPLIT ? head_walk_cap<DK, DV, NP>(g.heads) : 0;
+    return NR_OK;
+  }
   if (pass == FWD) {
     // FOUR waves per title, each taking heads w, w + 4, ...: the workgroup's 49.5 KB LDS image then
     // lets three titles share a CU (one wave per head, 12 waves at 104 VGPRs, fit one title per CU,
@@ -1168,7 +1348,8 @@ int launch_np(const MPArgs& g, Pass pass, hipStream_t s) {
     hipLaunchKernelGGL((mha_ln_bwd_kernel<NH64>), dim3((unsigned)g.nseq), dim3(256), 0, s, g);
     MPArgs g2 = g;
     g2.rows_per_wave = 1;
-    const unsigned gx = (unsigned)((g.nseq + HB_TITLES - 1) / HB_TITLES), gy = (unsigned)((g.heads + 3) / 4);
+    const int64_t cap = head_walk_cap<DK, DV, NP>(g.heads);
+    const unsigned gx = (unsigned)(g.nseq < cap ? g.nseq : cap), gy = (unsigned)((g.heads + 3) / 4);
     hipLaunchKernelGGL((mha_head_bwd_kernel<DK, DV, NP>), dim3(gx, gy), dim3(256), head_bwd_smem(4, DV), s, g2);
     if (g.ws) {
       const int NY = g.heads * (DK + DV);
@@ -1181,18 +1362,18 @@ int launch_np(const MPArgs& g, Pass pass, hipStream_t s) {
 
 // the attention products' arithmetic follows the caller's GEMM precision (nr_gemm_precision)
 template <int DK, int DV, int NH64>
-int launch(const MPArgs& g, Pass pass, hipStream_t s) {
-  if (g.np == 3) return launch_np<DK, DV, NH64, 3>(g, pass, s);
-  if (g.np == 1) return launch_np<DK, DV, NH64, 1>(g, pass, s);
-  return launch_np<DK, DV, NH64, 0>(g, pass, s);
+int launch(const MPArgs& g, Pass pass, hipStream_t s, int* walk) {
+  if (g.np == 3) return launch_np<DK, DV, NH64, 3>(g, pass, s, walk);
+  if (g.np == 1) return launch_np<DK, DV, NH64, 1>(g, pass, s, walk);
+  return launch_np<DK, DV, NH64, 0>(g, pass, s, walk);
 }
 
-int dispatch(const MPArgs& g, int dk, int dv, Pass pass, hipStream_t s) {
+int dispatch(const MPArgs& g, int dk, int dv, Pass pass, hipStream_t s, int* walk = nullptr) {
   const int H = g.heads * dv;
   if (H % 64) return NR_EINVAL(9);
   const int nh64 = H / 64;
 #define NR_CASE(K, V, N) \
-  if (dk == K && dv == V && nh64 == N) return launch<K, V, N>(g, pass, s);
+  if (dk == K && dv == V && nh64 == N) return launch<K, V, N>(g, pass, s, walk);
   NR_CASE(64, 32, 6)    // NRMS news encoder: E=768 -> 12 heads x 64, H = 384
   NR_CASE(64, 64, 12)   // H = 768
   NR_CASE(64, 32, 4)    // H = 256 (8 heads)
@@ -1296,4 +1477,17 @@ extern "C" int nr_mha_pool_bwd(const float* y, int64_t ldy, const int64_t* yrows
   g.ws = ws; g.ws_copies = ws_copies;
   g.ws_ld = ((int64_t)3 * heads * dv + (int64_t)heads * (dk + dv) + 3) & ~int64_t(3);
   return dispatch(g, dk, dv, o && dob ? BWD_SPLIT : BWD_FUSED, stream);
+}
+
+extern "C" int nr_mha_pool_walk_workgroups(int32_t pass, int32_t heads, int32_t dk, int32_t dv, int32_t prec) {
+  if (heads < 1 || heads > 12) return NR_EINVAL(0);
+  if (prec != NR_GEMM_F32 && prec != NR_GEMM_BF16X6 && prec != NR_GEMM_BF16) return NR_EINVAL(4);
+  if (pass != FWD && pass != BWD_FUSED && pass != BWD_SPLIT) return NR_EINVAL(1);
+  MPArgs g{};
+  g.heads = heads;
+  // the precision each pass runs its products in (nr_mha_pool_fwd / nr_mha_pool_bwd)
+  g.np = prec == NR_GEMM_BF16 ? 1 : prec == NR_GEMM_BF16X6 && pass == FWD ? 3 : 0;
+  int walk = 0;
+  const int rc = dispatch(g, dk, dv, (Pass)pass, nullptr, &walk);
+  return rc != NR_OK ? rc : walk;
 }
