@@ -20,6 +20,8 @@
 // which is the row accumulator register s of lane half h holds.  The contraction over the 64
 // head dims uses dim 32h + s in k-step s (the order is free), so every operand fragment is 32
 // consecutive floats of one row.
+#include <type_traits>
+
 #include "common.h"
 #include "mfma_planes.h"
 #include "../../include/newsrec_hip.h"
@@ -749,11 +751,14 @@ __global__ void __launch_bounds__(256) attn_bwd_q_kernel(AttnArgs g) {
 //     holds belongs to -- so the tile is staged TRANSPOSED (dims x rows) and read as two 4-row runs
 //     per plane (colfrag).
 // Every staged element is split once per tile by the staging threads, not once per wave.
-// compile-time A/B knob (tools/build_ab.sh): the dK/dV pass of four-wave sequences as eight-wave workgroups
-#ifndef NR_ATTN_BWD_W8
-#define NR_ATTN_BWD_W8 1
-#endif
-constexpr bool kNrAttnBwdW8 = NR_ATTN_BWD_W8;
+// Two forms per kernel, chosen by the host from the sequence length (attn_long): the short one (L <= 96,
+// e.g. the 30-token titles) runs one to three waves and stages each tile between its two barriers
+// (stage_planes); LONG (the 501-token user sequence) prefetches the next tile into registers
+// (TileFetch), runs forward and dK/dV pass as eight-wave workgroups whose two halves stage one tensor
+// each, and passes dS from the dK/dV pass to the dQ pass as tiles (attn_bwd_q_ds_kernel).
+// Dropout of the probabilities in the backward kernels: none, the per-element hash, or the keep bits
+// the forward stored (g.keep; the launcher checks).
+enum DropMode { kDropNone, kDropHash, kDropBits };
 constexpr int kKR = kHD + 8;   // row-major plane row: 64 dims + 8 pad (144 B: ds_read_b128 conflict-free)
 constexpr int kVR = 36;        // transposed plane row: 32 rows + 4 pad (72 B: ds_read_b64 conflict-free)
 
@@ -896,7 +901,7 @@ __device__ __forceinline__ void own_rows(Planes<NP> (&out)[4], const float* p, b
   for (int t = 0; t < 4; ++t) out[t] = planes8<NP>(f + 8 * t);
 }
 
-// Register-prefetched staging (workgroups of four waves): thread f holds rows 2 kp, 2 kp + 1 and dims
+// Register-prefetched staging (the LONG forms): thread f holds rows 2 kp, 2 kp + 1 and dims
 // 4 dq .. 4 dq + 3 (tile_slot) of the NEXT tile of one tensor, loaded while the current
 // tile's products run, and writes both plane images of it from one split after the barrier.  Without
 // it every tile paid a full load latency between its two barriers (one to three waves per SIMD
@@ -947,10 +952,10 @@ __device__ __forceinline__ float key_add(const AttnArgs& g, int64_t row0, int j,
 
 // (232 VGPRs: two waves per SIMD.  Bounded to three, 13 spilled and the XFormer step did not move,
 // 69.0 vs 69.1 ms, profiles/r04_p_xf_ab.json.)
-// W8 (the 501-token user sequence): eight-wave workgroups, threads 0..255 stage K and 256..511 V, so
-// each K / V tile is split once per 256 queries instead of per 128 and each thread splits one tensor.
-template <int NP, bool DROP, bool PF, bool W8 = false>
-__global__ void __launch_bounds__(W8 ? 512 : 256) attn_fwd_mp_kernel(AttnArgs g) {
+// LONG: eight-wave workgroups, threads 0..255 stage K and 256..511 V, so each K / V tile is split once
+// per 256 queries instead of per 128 and each thread splits one tensor.
+template <int NP, bool DROP, bool LONG>
+__global__ void __launch_bounds__(LONG ? 512 : 256) attn_fwd_mp_kernel(AttnArgs g) {
   __shared__ __attribute__((aligned(16))) uint16_t Kp[NP][32][kKR];
   __shared__ __attribute__((aligned(16))) uint16_t Vt[NP][kHD][kVR];
   __shared__ float kadd[32];
@@ -975,37 +980,22 @@ __global__ void __launch_bounds__(W8 ? 512 : 256) attn_fwd_mp_kernel(AttnArgs g)
   for (int r = 0; r < 16; ++r) o0[r] = o1[r] = 0.f;
   float m = -INFINITY, l = 0.f;
   const int nkb = (L + 31) / 32;
-  TileFetch<NP> fk, fv;
+  TileFetch<NP> fk;
   float kadd_n = 0.f;
-  const bool kside = threadIdx.x < 256;   // W8: this thread stages K (else V)
+  const bool kside = threadIdx.x < 256;   // LONG: this thread stages K (else V)
   const int64_t wcol = (kside ? g.koff : g.voff) + head * kHD;
-  if constexpr (PF) {
-    if constexpr (W8) {
-      fk.fetch(g.qkv, g.ldq, row0, 0, L, wcol);
-    } else {
-      fk.fetch(g.qkv, g.ldq, row0, 0, L, g.koff + head * kHD);
-      fv.fetch(g.qkv, g.ldq, row0, 0, L, g.voff + head * kHD);
-    }
+  if constexpr (LONG) {
+    fk.fetch(g.qkv, g.ldq, row0, 0, L, wcol);
     if (threadIdx.x < 32) kadd_n = key_add(g, row0, threadIdx.x, L);
   }
   for (int kb = 0; kb < nkb; ++kb) {
     __syncthreads();
-    if constexpr (PF) {
-      if constexpr (W8) {
-        if (kside) fk.store(Kp, nullptr);
-        else fk.store(nullptr, Vt);
-      } else {
-        fk.store(Kp, nullptr);
-        fv.store(nullptr, Vt);
-      }
+    if constexpr (LONG) {
+      if (kside) fk.store(Kp, nullptr);
+      else fk.store(nullptr, Vt);
       if (threadIdx.x < 32) kadd[threadIdx.x] = kadd_n;
       if (kb + 1 < nkb) {
-        if constexpr (W8) {
-          fk.fetch(g.qkv, g.ldq, row0, (kb + 1) * 32, L, wcol);
-        } else {
-          fk.fetch(g.qkv, g.ldq, row0, (kb + 1) * 32, L, g.koff + head * kHD);
-          fv.fetch(g.qkv, g.ldq, row0, (kb + 1) * 32, L, g.voff + head * kHD);
-        }
+        fk.fetch(g.qkv, g.ldq, row0, (kb + 1) * 32, L, wcol);
         if (threadIdx.x < 32) kadd_n = key_add(g, row0, (kb + 1) * 32 + threadIdx.x, L);
       }
     } else {
@@ -1084,16 +1074,18 @@ __global__ void __launch_bounds__(W8 ? 512 : 256) attn_fwd_mp_kernel(AttnArgs g)
 // Two waves per SIMD, as attn_bwd_q_mp_kernel: with the own K / V rows held as split planes (96
 // VGPRs) the bound spilled 36 and ran slower (profiles/r04_o_xf_ab.json); held as fp32 and split per
 // query tile it spills 9 and the XFormer step gains 68.15 -> 67.86 ms (profiles/r04_q_xf_ab.json).
-// W8 (the 501-token user sequence): eight-wave workgroups, threads 0..255 stage the Q tile and 256..511
-// the dctx tile, so each query tile is split once per 256 keys instead of per 128 (as the forward's W8).
-template <int NP, bool DROP, bool PF, bool KB = false, bool DS = false, bool W8 = false>
-__global__ void __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(2))) attn_bwd_kv_mp_kernel(AttnArgs g) {
+// LONG: eight-wave workgroups, threads 0..255 stage the Q tile and 256..511 the dctx tile, so each query
+// tile is split once per 256 keys instead of per 128 (as the forward's; four-wave workgroups measured
+// 385 vs 366 us per launch, profiles/r06_t/README.md), and every dS tile is stored to g.dsb for
+// attn_bwd_q_ds_kernel.
+template <int NP, DropMode DM, bool LONG>
+__global__ void __launch_bounds__(LONG ? 512 : 256) __attribute__((amdgpu_waves_per_eu(2))) attn_bwd_kv_mp_kernel(AttnArgs g) {
   __shared__ __attribute__((aligned(16))) uint16_t Qp[NP][32][kKR];
   __shared__ __attribute__((aligned(16))) uint16_t Op[NP][32][kKR];
   __shared__ __attribute__((aligned(16))) uint16_t Qt[NP][kHD][kVR];
   __shared__ __attribute__((aligned(16))) uint16_t Ot[NP][kHD][kVR];
   __shared__ float qm[32], qi[32], qd[32];
-  __shared__ __attribute__((aligned(16))) uint32_t kwd[W8 ? 8 : 4][32];   // per wave: the tile's 32 queries' words of its key tile
+  __shared__ __attribute__((aligned(16))) uint32_t kwd[LONG ? 8 : 4][32];   // per wave: the tile's 32 queries' words of its key tile
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 31, hh = lane >> 5;
   const int nw = blockDim.x >> 6;
   int64_t bid = blockIdx.x;
@@ -1107,6 +1099,7 @@ __global__ void __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_pe
   const bool active = k0 < L;
   const int key = k0 + c;
   const bool own = active && key < L;
+  constexpr bool DROP = DM != kDropNone, kbits = DM == kDropBits;
   const uint32_t dkey = DROP ? attn_key(g, seq, head) : 0u;
 
   // the wave's own K / V half-rows kept as fp32 and split per use (planes held for all four steps of
@@ -1125,14 +1118,13 @@ __global__ void __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_pe
   }
   const float kadd = own ? (nr_mask_at(g.mask, g.mdt, row0 + key) ? 0.f : kNegMax) : -INFINITY;
   // stored keep bits: lane c's key is bit ((c >> 3) << 2 | (c & 3)) + 16 ((c >> 2) & 1) of a query's word
-  constexpr bool kbits = DROP && KB;   // KB: g.keep holds the forward's bits (the launcher checks)
   const int kbit = (((c >> 3) << 2) | (c & 3)) + 16 * ((c >> 2) & 1);
   const int kbt = k0 >> 5;   // this wave's key tile
   auto kword = [&](int j) -> uint32_t {   // query j's word of this wave's key tile (0 past L)
     return j < L && active ? g.keep[keep_word(g, seq, head, j, kbt)] : 0u;
   };
   uint32_t kw_n = 0u;
-  if (kbits && PF && lane < 32) kw_n = kword(lane);
+  if (kbits && LONG && lane < 32) kw_n = kword(lane);
   f32x16 dk0, dk1, dv0, dv1;
 #pragma unroll
   for (int r = 0; r < 16; ++r) dk0[r] = dk1[r] = dv0[r] = dv1[r] = 0.f;
@@ -1150,30 +1142,20 @@ __global__ void __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_pe
       d = 0.f;
     }
   };
-  TileFetch<NP> fq, fo;
+  TileFetch<NP> fq;
   float qm_n = 0.f, qi_n = 0.f, qd_n = 0.f;
-  const bool qside = threadIdx.x < 256;   // W8: this thread stages Q (else dctx)
+  const bool qside = threadIdx.x < 256;   // LONG: this thread stages Q (else dctx)
   const float* wbase = qside ? g.qkv : g.dctx;
   const int64_t wld = qside ? g.ldq : g.ldd;
-  if constexpr (PF) {
-    if constexpr (W8) {
-      fq.fetch(wbase, wld, row0, 0, L, head * kHD);
-    } else {
-      fq.fetch(g.qkv, g.ldq, row0, 0, L, head * kHD);
-      fo.fetch(g.dctx, g.ldd, row0, 0, L, head * kHD);
-    }
+  if constexpr (LONG) {
+    fq.fetch(wbase, wld, row0, 0, L, head * kHD);
     if (threadIdx.x < 32) qstats(threadIdx.x, qm_n, qi_n, qd_n);
   }
   for (int qb = 0; qb < nqb; ++qb) {
     __syncthreads();
-    if constexpr (PF) {
-      if constexpr (W8) {
-        if (qside) fq.store(Qp, Qt);
-        else fq.store(Op, Ot);
-      } else {
-        fq.store(Qp, Qt);
-        fo.store(Op, Ot);
-      }
+    if constexpr (LONG) {
+      if (qside) fq.store(Qp, Qt);
+      else fq.store(Op, Ot);
       if (threadIdx.x < 32) {
         qm[threadIdx.x] = qm_n;
         qi[threadIdx.x] = qi_n;
@@ -1181,12 +1163,7 @@ __global__ void __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_pe
       }
       if (kbits && lane < 32) kwd[wave][lane] = kw_n;
       if (qb + 1 < nqb) {
-        if constexpr (W8) {
-          fq.fetch(wbase, wld, row0, (qb + 1) * 32, L, head * kHD);
-        } else {
-          fq.fetch(g.qkv, g.ldq, row0, (qb + 1) * 32, L, head * kHD);
-          fo.fetch(g.dctx, g.ldd, row0, (qb + 1) * 32, L, head * kHD);
-        }
+        fq.fetch(wbase, wld, row0, (qb + 1) * 32, L, head * kHD);
         if (threadIdx.x < 32) qstats((qb + 1) * 32 + threadIdx.x, qm_n, qi_n, qd_n);
         if (kbits && lane < 32) kw_n = kword((qb + 1) * 32 + lane);
       }
@@ -1241,7 +1218,7 @@ __global__ void __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_pe
       pd[r] = pdr;
       ds[r] = pr * (d - qd[qr]);
     }
-    if constexpr (DS) {   // one 128 B row (query) per half-wave and r, unconditional: keys past L
+    if constexpr (LONG) {   // one 128 B row (query) per half-wave and r, unconditional: keys past L
       // and the padding queries L .. 32 nkb - 1 store 0 (p = 0 there)
       float* dsp = g.dsb + (((seq * g.heads + head) * (int64_t)g.nkb + kbt) * g.nkb + qb) * 1024 + c;
 #pragma unroll
@@ -1276,7 +1253,8 @@ __global__ void __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_pe
 // Two waves per SIMD: unbounded, the bf16x6 prefetching form took 270 VGPRs -- one wave per SIMD,
 // its softmax / dS arithmetic never overlapping another wave's MFMAs; at <= 256 it fits without
 // spills: XFormer step 71.5 -> 69.9 ms on one box (profiles/r04_o_xf_ab.json).
-template <int NP, bool DROP, bool PF, bool KB = false>
+// The short form only: the LONG dQ pass is attn_bwd_q_ds_kernel.
+template <int NP, DropMode DM>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) attn_bwd_q_mp_kernel(AttnArgs g) {
   __shared__ __attribute__((aligned(16))) uint16_t Kp[NP][32][kKR];
   __shared__ __attribute__((aligned(16))) uint16_t Vp[NP][32][kKR];
@@ -1295,6 +1273,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) a
   const bool active = q0 < L;
   const int q = q0 + c;
   const bool own = active && q < L;
+  constexpr bool DROP = DM != kDropNone, kbits = DM == kDropBits;
   const uint32_t dkey = DROP ? attn_key(g, seq, head) : 0u;
 
   Planes<NP> qp4[4], dp4[4];
@@ -1312,34 +1291,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) a
   for (int r = 0; r < 16; ++r) a0[r] = a1[r] = 0.f;
   const int nkb = (L + 31) / 32;
   // stored keep bits: this lane's half of its query's word of each key tile, loaded a tile ahead
-  constexpr bool kbits = DROP && KB;   // KB: g.keep holds the forward's bits (the launcher checks)
   auto kword = [&](int kb) -> uint32_t { return own ? g.keep[keep_word(g, seq, head, q, kb)] >> (16 * hh) : 0u; };
   uint32_t kw_c = kbits ? kword(0) : 0u;
-  TileFetch<NP> fk, fv;
-  float kadd_n = 0.f;
-  if constexpr (PF) {
-    fk.fetch(g.qkv, g.ldq, row0, 0, L, g.koff + head * kHD);
-    fv.fetch(g.qkv, g.ldq, row0, 0, L, g.voff + head * kHD);
-    if (threadIdx.x < 32) kadd_n = key_add(g, row0, threadIdx.x, L);
-  }
   for (int kb = 0; kb < nkb; ++kb) {
     const uint32_t kw = kw_c;
     if (kbits && kb + 1 < nkb) kw_c = kword(kb + 1);
     __syncthreads();
-    if constexpr (PF) {
-      fk.store(Kp, Kt);
-      fv.store(Vp, nullptr);
-      if (threadIdx.x < 32) kadd[threadIdx.x] = kadd_n;
-      if (kb + 1 < nkb) {
-        fk.fetch(g.qkv, g.ldq, row0, (kb + 1) * 32, L, g.koff + head * kHD);
-        fv.fetch(g.qkv, g.ldq, row0, (kb + 1) * 32, L, g.voff + head * kHD);
-        if (threadIdx.x < 32) kadd_n = key_add(g, row0, (kb + 1) * 32 + threadIdx.x, L);
-      }
-    } else {
-      stage_planes<NP>(Kp, Kt, g.qkv, g.ldq, row0, kb * 32, L, g.koff + head * kHD);
-      stage_planes<NP>(Vp, nullptr, g.qkv, g.ldq, row0, kb * 32, L, g.voff + head * kHD);
-      if (threadIdx.x < 32) kadd[threadIdx.x] = key_add(g, row0, kb * 32 + threadIdx.x, L);
-    }
+    stage_planes<NP>(Kp, Kt, g.qkv, g.ldq, row0, kb * 32, L, g.koff + head * kHD);
+    stage_planes<NP>(Vp, nullptr, g.qkv, g.ldq, row0, kb * 32, L, g.voff + head * kHD);
+    if (threadIdx.x < 32) kadd[threadIdx.x] = key_add(g, row0, kb * 32 + threadIdx.x, L);
     __syncthreads();
     if (!active) continue;
     f32x16 s, dp;
@@ -1387,7 +1347,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) a
   }
 }
 
-// dQ = dS K from the dS tiles attn_bwd_kv_mp_kernel<..., DS = true> stored (four-wave launches, the
+// dQ = dS K from the dS tiles attn_bwd_kv_mp_kernel<..., LONG = true> stored (four-wave launches, the
 // 501-token user sequence): a wave owns 32 queries; per key tile only K is staged (transposed) and
 // lane (c, h) loads its query's 16 dS values of the tile (four float4, a tile ahead) -- no S, P, dP
 // recompute, no dropout hash, no Q / dctx planes in registers.
@@ -1488,6 +1448,23 @@ int attn_waves(int L) {
   return w < 4 ? w : 4;
 }
 
+// the LONG form of the MFMA kernels: sequences of four waves (L > 96); the f32 kernels have one form
+bool attn_long(int L, int32_t prec) { return attn_waves(L) == 4 && prec != NR_GEMM_F32; }
+
+// f(NP, mode, long) with the three run-time values of an MFMA attention launch as compile-time constants
+template <class F>
+void attn_route(int32_t prec, DropMode mode, bool lng, F f) {
+  auto with_long = [&](auto np, auto dm) {
+    lng ? f(np, dm, std::true_type{}) : f(np, dm, std::false_type{});
+  };
+  auto with_mode = [&](auto np) {
+    if (mode == kDropNone) with_long(np, std::integral_constant<DropMode, kDropNone>{});
+    else if (mode == kDropHash) with_long(np, std::integral_constant<DropMode, kDropHash>{});
+    else with_long(np, std::integral_constant<DropMode, kDropBits>{});
+  };
+  prec == NR_GEMM_BF16 ? with_mode(std::integral_constant<int, 1>{}) : with_mode(std::integral_constant<int, 3>{});
+}
+
 }  // namespace
 
 // ==================================================================================== C ABI
@@ -1574,31 +1551,19 @@ extern "C" int nr_bert_attn_fwd(const float* qkv, int64_t ldq, int64_t koff, int
   if (nseq == 0) return NR_OK;
   g.ctx = ctx; g.ldc = ldc;
   g.keep = p_drop > 0.f ? keep : nullptr; g.nkb = (L + 31) / 32;
-  // four-wave sequences (L > 96) with the MFMA arithmetic run as eight-wave workgroups (W8)
-  const int nw = attn_waves(L) == 4 && prec != NR_GEMM_F32 ? 8 : attn_waves(L);
+  const bool lng = attn_long(L, prec);
+  const int nw = lng ? 8 : attn_waves(L);   // the LONG forward runs eight-wave workgroups
   g.chunks = (L + 32 * nw - 1) / (32 * nw);
   const dim3 grid((unsigned)(nseq * heads * g.chunks)), block(64 * nw);
   const bool drop = p_drop > 0.f;
-#define NR_FWD(KER) hipLaunchKernelGGL(KER, grid, block, 0, stream, g)
   if (prec == NR_GEMM_F32) {
-    if (drop) NR_FWD(attn_fwd_kernel<true>);
-    else NR_FWD(attn_fwd_kernel<false>);
-  } else if (nw == 8) {
-    if (prec == NR_GEMM_BF16) {
-      if (drop) NR_FWD((attn_fwd_mp_kernel<1, true, true, true>));
-      else NR_FWD((attn_fwd_mp_kernel<1, false, true, true>));
-    } else {
-      if (drop) NR_FWD((attn_fwd_mp_kernel<3, true, true, true>));
-      else NR_FWD((attn_fwd_mp_kernel<3, false, true, true>));
-    }
-  } else if (prec == NR_GEMM_BF16) {
-    if (drop) NR_FWD((attn_fwd_mp_kernel<1, true, false>));
-    else NR_FWD((attn_fwd_mp_kernel<1, false, false>));
-  } else {
-    if (drop) NR_FWD((attn_fwd_mp_kernel<3, true, false>));
-    else NR_FWD((attn_fwd_mp_kernel<3, false, false>));
+    if (drop) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, block, 0, stream, g);
+    else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, block, 0, stream, g);
+  } else {   // (hashes, and stores the bits where g.keep is set: one dropping form)
+    attn_route(prec, drop ? kDropHash : kDropNone, lng, [&](auto np, auto dm, auto lg) {
+      hipLaunchKernelGGL((attn_fwd_mp_kernel<np(), dm() != kDropNone, lg()>), grid, block, 0, stream, g);
+    });
   }
-#undef NR_FWD
   NR_LAUNCH_CHECK();
   return NR_OK;
 }
@@ -1612,7 +1577,8 @@ extern "C" int64_t nr_bert_attn_bwd_workspace(int64_t nseq, int32_t L, int32_t h
   if (nseq < 0 || L <= 0 || heads <= 0) return 0;
   int64_t f = attn_dq_floats(nseq, L, heads);
   const int64_t nkb = (L + 31) / 32;
-  if (attn_waves(L) == 4) f += nseq * heads * nkb * nkb * 1024;   // dS tiles
+  // dS tiles of the LONG form; there is no prec here, so an f32 caller's are allocated and never used
+  if (attn_waves(L) == 4) f += nseq * heads * nkb * nkb * 1024;
   return f * (int64_t)sizeof(float);
 }
 
@@ -1642,53 +1608,28 @@ extern "C" int nr_bert_attn_bwd(const float* qkv, int64_t ldq, int64_t koff, int
   g.chunks = (L + 32 * nw - 1) / (32 * nw);
   const dim3 grid((unsigned)(nseq * heads * g.chunks)), block(64 * nw);
   const bool drop = p_drop > 0.f;
-  // the dK/dV pass of four-wave sequences with the MFMA arithmetic runs as eight-wave workgroups (W8)
-  const bool w8 = nw == 4 && prec != NR_GEMM_F32 && kNrAttnBwdW8;   // (the f32 kernels are 256-thread)
+  // the LONG dK/dV pass runs eight-wave workgroups (the dQ pass and the f32 kernels are 256-thread)
+  const bool lng = attn_long(L, prec);
   AttnArgs gkv = g;
-  gkv.chunks = w8 ? (L + 255) / 256 : g.chunks;
-  const dim3 gridkv((unsigned)(nseq * heads * gkv.chunks)), blockkv(w8 ? 512 : 64 * nw);
-#define NR_BWD(KV, Q)                                          \
-  do {                                                         \
-    hipLaunchKernelGGL(KV, gridkv, blockkv, 0, stream, gkv);   \
-    hipLaunchKernelGGL(Q, grid, block, 0, stream, g);          \
-  } while (0)
-  const bool kb = drop && g.keep != nullptr;
+  gkv.chunks = lng ? (L + 255) / 256 : g.chunks;
+  const dim3 gridkv((unsigned)(nseq * heads * gkv.chunks)), blockkv(lng ? 512 : 64 * nw);
   if (prec == NR_GEMM_F32) {
-    if (drop) NR_BWD(attn_bwd_kv_kernel<true>, attn_bwd_q_kernel<true>);
-    else NR_BWD(attn_bwd_kv_kernel<false>, attn_bwd_q_kernel<false>);
-  } else if (kb && w8) {   // the forward's keep bits instead of the per-element hash
-    if (prec == NR_GEMM_BF16) NR_BWD((attn_bwd_kv_mp_kernel<1, true, true, true, true, true>), attn_bwd_q_ds_kernel<1>);
-    else NR_BWD((attn_bwd_kv_mp_kernel<3, true, true, true, true, true>), attn_bwd_q_ds_kernel<3>);
-  } else if (kb && nw == 4) {
-    if (prec == NR_GEMM_BF16) NR_BWD((attn_bwd_kv_mp_kernel<1, true, true, true, true>), attn_bwd_q_ds_kernel<1>);
-    else NR_BWD((attn_bwd_kv_mp_kernel<3, true, true, true, true>), attn_bwd_q_ds_kernel<3>);
-  } else if (kb) {
-    if (prec == NR_GEMM_BF16) NR_BWD((attn_bwd_kv_mp_kernel<1, true, false, true>), (attn_bwd_q_mp_kernel<1, true, false, true>));
-    else NR_BWD((attn_bwd_kv_mp_kernel<3, true, false, true>), (attn_bwd_q_mp_kernel<3, true, false, true>));
-  } else if (w8) {
-    if (prec == NR_GEMM_BF16) {
-      if (drop) NR_BWD((attn_bwd_kv_mp_kernel<1, true, true, false, true, true>), attn_bwd_q_ds_kernel<1>);
-      else NR_BWD((attn_bwd_kv_mp_kernel<1, false, true, false, true, true>), attn_bwd_q_ds_kernel<1>);
+    if (drop) {
+      hipLaunchKernelGGL(attn_bwd_kv_kernel<true>, gridkv, blockkv, 0, stream, gkv);
+      hipLaunchKernelGGL(attn_bwd_q_kernel<true>, grid, block, 0, stream, g);
     } else {
-      if (drop) NR_BWD((attn_bwd_kv_mp_kernel<3, true, true, false, true, true>), attn_bwd_q_ds_kernel<3>);
-      else NR_BWD((attn_bwd_kv_mp_kernel<3, false, true, false, true, true>), attn_bwd_q_ds_kernel<3>);
+      hipLaunchKernelGGL(attn_bwd_kv_kernel<false>, gridkv, blockkv, 0, stream, gkv);
+      hipLaunchKernelGGL(attn_bwd_q_kernel<false>, grid, block, 0, stream, g);
     }
-  } else if (nw == 4) {
-    if (prec == NR_GEMM_BF16) {
-      if (drop) NR_BWD((attn_bwd_kv_mp_kernel<1, true, true, false, true>), attn_bwd_q_ds_kernel<1>);
-      else NR_BWD((attn_bwd_kv_mp_kernel<1, false, true, false, true>), attn_bwd_q_ds_kernel<1>);
-    } else {
-      if (drop) NR_BWD((attn_bwd_kv_mp_kernel<3, true, true, false, true>), attn_bwd_q_ds_kernel<3>);
-      else NR_BWD((attn_bwd_kv_mp_kernel<3, false, true, false, true>), attn_bwd_q_ds_kernel<3>);
-    }
-  } else if (prec == NR_GEMM_BF16) {
-    if (drop) NR_BWD((attn_bwd_kv_mp_kernel<1, true, false>), (attn_bwd_q_mp_kernel<1, true, false>));
-    else NR_BWD((attn_bwd_kv_mp_kernel<1, false, false>), (attn_bwd_q_mp_kernel<1, false, false>));
   } else {
-    if (drop) NR_BWD((attn_bwd_kv_mp_kernel<3, true, false>), (attn_bwd_q_mp_kernel<3, true, false>));
-    else NR_BWD((attn_bwd_kv_mp_kernel<3, false, false>), (attn_bwd_q_mp_kernel<3, false, false>));
+    // the forward's keep bits, where the caller kept them, instead of the per-element hash
+    const DropMode mode = !drop ? kDropNone : g.keep ? kDropBits : kDropHash;
+    attn_route(prec, mode, lng, [&](auto np, auto dm, auto lg) {
+      hipLaunchKernelGGL((attn_bwd_kv_mp_kernel<np(), dm(), lg()>), gridkv, blockkv, 0, stream, gkv);
+      if constexpr (lg()) hipLaunchKernelGGL(attn_bwd_q_ds_kernel<np()>, grid, block, 0, stream, g);
+      else hipLaunchKernelGGL((attn_bwd_q_mp_kernel<np(), dm()>), grid, block, 0, stream, g);
+    });
   }
-#undef NR_BWD
   NR_LAUNCH_CHECK();
   return NR_OK;
 }

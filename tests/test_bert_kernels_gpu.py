@@ -435,7 +435,7 @@ def _layout(H, layout):
     return (0, H, 2 * H, 3 * H + 8) if layout == "default" else (H + 4, 2 * H + 8, 0, 3 * H + 12)
 
 
-def run_attn(c, prec, layout="default", mask=None, rng=None, seed=None, offset=None):
+def run_attn(c, prec, layout="default", mask=None, rng=None, seed=None, offset=None, keep=False):
     from newsrec_amd import _lib as Lb, kernels as K
     mode = {"f32": Lb.GEMM_F32, "bf16x6": Lb.GEMM_BF16X6, "bf16": Lb.GEMM_BF16}[prec]
     T, H, heads, inp = c.T, c.H, c.heads, c.inp
@@ -447,6 +447,8 @@ def run_attn(c, prec, layout="default", mask=None, rng=None, seed=None, offset=N
     m = (c.mask if mask is None else mask).cuda()
     ctx, ml = _nan(T, H + 4), _vec(2 * T * heads)
     drop = _drop_args(c, rng, seed, offset)
+    if keep:    # the forward stores its dropout keep bits, the backward reads them instead of hashing
+        drop["keep"] = K.bert_attn_keep_buffer(c.nseq, c.L, heads, "cuda")
     K.bert_attn_fwd(buf[:, qo:], heads, m, c.nseq, c.L, ctx[:, :H], ml[1], prec=mode, **off, **drop)
     K.bert_attn_bwd(buf[:, qo:], heads, m, c.nseq, c.L, ctx[:, :H], ml[1], _padded(inp["dctx"], 8), dbuf[:, qo:],
                     prec=mode, **off, **drop)
@@ -483,6 +485,38 @@ def check_attn(c, o, what, prec, layout="default"):
 def test_attention_vs_reference(L, heads, prec, p):
     c = attn_case(L, heads, p)
     check_attn(c, run_attn(c, prec), "vs-ref", prec)
+
+
+# the smallest shapes that reach: a single-slot keep word; two key tiles on the short route; the last short
+# length; the first long length; two query chunks of the four-wave dQ pass beside one eight-wave chunk; two
+# eight-wave chunks
+KEEP_SHAPES = [(1, 1), (33, 3), (96, 3), (97, 3), (129, 3), (257, 3)]
+
+
+@pytest.mark.parametrize("L,heads", KEEP_SHAPES, ids=["L%d-h%d" % c for c in KEEP_SHAPES])
+@pytest.mark.parametrize("prec", ["bf16x6", "bf16"])
+def test_attention_keep_bits(prec, L, heads):
+    """The route the BERT tower runs: the bf16-MFMA forward stores the dropout keep bits (K.bert_attn_keep_buffer)
+    and both backward kernels read them instead of re-hashing every probability's counter.  Against the float64
+    reference at the bar of every other attention case, and bit for bit the hashed run of the same case: the
+    masks are the same either way and the arithmetic after the mask is identical."""
+    c = attn_case(L, heads, P_DROP)
+    o = run_attn(c, prec, keep=True)
+    check_attn(c, o, "keep-bits", prec)
+    h = run_attn(c, prec)
+    for name in ("ctx", "ml", "dqkv"):
+        assert _bits_equal(o[name], h[name]), "%s: stored keep bits vs the hash" % name
+
+
+def test_attention_keep_bits_f32_rejected():
+    """The f32 forward stores no keep bits: a keep buffer with prec = f32 is refused before any launch."""
+    from newsrec_amd import _lib as Lb, kernels as K
+    c = attn_case(33, 3, P_DROP)
+    buf = torch.zeros(c.T, 3 * c.H, device="cuda")
+    ctx, ml = torch.zeros(c.T, c.H, device="cuda"), torch.zeros(2 * c.T * c.heads, device="cuda")
+    with pytest.raises(Lb.HipError, match="invalid argument 7"):
+        K.bert_attn_fwd(buf, c.heads, c.mask.cuda(), c.nseq, c.L, ctx, ml, prec=Lb.GEMM_F32,
+                        keep=K.bert_attn_keep_buffer(c.nseq, c.L, c.heads, "cuda"), **_drop_args(c, None, None, None))
 
 
 @pytest.mark.parametrize("prec", ["f32", "bf16x6", "bf16"])

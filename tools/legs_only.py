@@ -17,7 +17,7 @@ from newsrec_amd import functions as F  # noqa: E402
 for kv in a.set:
     k, v = kv.split("=")
     mod = F
-    if "." in k:   # module.NAME (e.g. bert.ATTN_KEEP_BITS)
+    if "." in k:   # module.NAME (e.g. encoders.USER_POOL_FUSED)
         import importlib
         m, k = k.rsplit(".", 1)
         mod = importlib.import_module("newsrec_amd." + m)
