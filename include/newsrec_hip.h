@@ -320,7 +320,12 @@ int nr_cnn_keypool_bwd(const float* C, int64_t ldc, const float* wq, const float
  * {(64,32),(32,32),(64,64),(64,16),(16,16)} for L <= 32, {(32,32),(64,64),(16,16),(64,32)}
  * for L <= 64.  mask: [nseq, L] of enum nr_mask_dtype (0=u8, 1=i64, 2=f64, 3=f32).
  * rows (optional): token s*L+j reads qk / v row rows[s*L+j] (projections computed once per
- * distinct row, e.g. the fast-eval news table, and gathered inside the kernel). */
+ * distinct row, e.g. the fast-eval news table, and gathered inside the kernel).
+ * Returns, checked in this order and before anything is launched (nseq = 0 reports the same codes, then
+ * NR_OK): -1000 L outside 1..64, heads outside 1..65535, nseq < 0 or > 2^31 - 1 (the grid's extents),
+ * mask_dtype outside 0..3; -1001 a NULL qk, v, mask or out; -1002 a pointer off 16 B, a leading dimension
+ * that is no multiple of 4 or smaller than its row (heads*dk for qk, heads*dv for v and out); -1008 a
+ * (dk, dv) outside the table above. */
 int nr_mha_attn_fwd(const float* qk, int64_t ld_qk, const float* v, int64_t ld_v,
                     const int64_t* rows, const void* mask, int32_t mask_dtype, int64_t nseq, int32_t L,
                     int32_t heads, int32_t dk, int32_t dv, float scale, float* out,
@@ -334,7 +339,12 @@ int nr_mha_attn_fwd(const float* qk, int64_t ld_qk, const float* v, int64_t ld_v
  *   out[s] = Σ_l XSoftmax(q · O_{s,l} / sqrt(heads*dv), m)_l O_{s,l}.
  * One workgroup per sequence, the attention products on the matrix cores in `prec` (nr_gemm_precision
  * values; bf16x6 = fp32-class).  L <= 64; (dk, dv, heads*dv) in {(32,32,384), (64,32,384), (64,64,768)};
- * y_rows = rows of y (y_rows * ldy * 4 < 2^32); yrows NULL = identity.  No autograd (eval only). */
+ * y_rows = rows of y (y_rows * ldy * 4 < 2^32); yrows NULL = identity.  No autograd (eval only).
+ * Returns, in this order and before anything is launched (nseq = 0 reports the same codes, then NR_OK):
+ * -1000 L outside 1..64, heads outside 1..12, nseq < 0 or > 2^31 - 1, mask_dtype outside 0..3; -1005
+ * y_rows; -1004 prec; -1001 a NULL y, mask, q or out; -1002 ldy % 4, ldy < heads*(dk+dv) or y off 16 B;
+ * -1003 ldo < heads*dv; -1009 heads*dv % 64; -1010 O [L][heads*dv + 1] past the 160 KB of LDS (heads*dv =
+ * 768: L > 53); -1008 a geometry outside the table above. */
 int nr_mha_user_pool_fwd(const float* y, int64_t ldy, int64_t y_rows, const int64_t* yrows, const void* mask,
                          int32_t mask_dtype, int64_t nseq, int32_t L, int32_t heads, int32_t dk, int32_t dv,
                          const float* q, float* out, int64_t ldo, int32_t prec, hipStream_t stream);
@@ -343,7 +353,10 @@ int nr_mha_user_pool_fwd(const float* y, int64_t ldy, int64_t y_rows, const int6
  * recomputes P.  dqk receives the gradient of the shared key projection (both roles).
  * dbias_k [heads*dk] / dbias_v [heads*dv] (both or neither; device): the projection bias gradient
  * (keyProject / valueProject bias, Attention.py:107-108) ATOMICALLY ACCUMULATED as the column sums of
- * dqk / dv_out over the nseq*L rows (caller zeroes) -- the separate column-sum pass folded in. */
+ * dqk / dv_out over the nseq*L rows (caller zeroes) -- the separate column-sum pass folded in.
+ * Returns as nr_mha_attn_fwd (the leading dimensions of dout and dv_out at least heads*dv, of dqk at least
+ * heads*dk), with -1003 for one of dbias_k / dbias_v without the other, checked after -1002 and before
+ * -1008; nseq = 0 reports the same codes. */
 int nr_mha_attn_bwd(const float* qk, int64_t ld_qk, const float* v, int64_t ld_v,
                     const void* mask, int32_t mask_dtype, int64_t nseq, int32_t L,
                     int32_t heads, int32_t dk, int32_t dv, float scale, const float* dout,

@@ -540,10 +540,11 @@ int launch(const AttnArgs& g, bool bwd, hipStream_t s) {
   return NR_OK;
 }
 
-int dispatch(const AttnArgs& g, int dk, int dv, bool bwd, hipStream_t s) {
+// probe: nothing is launched, NR_OK says that (lmax, dk, dv) has an instantiation
+int dispatch(const AttnArgs& g, int dk, int dv, bool bwd, hipStream_t s, bool probe = false) {
   const int lmax = g.L <= 32 ? 32 : 64;
 #define NR_CASE(LM, K, V) \
-  if (lmax == LM && dk == K && dv == V) return launch<LM, K, V>(g, bwd, s);
+  if (lmax == LM && dk == K && dv == V) return probe ? NR_OK : launch<LM, K, V>(g, bwd, s);
   NR_CASE(32, 64, 32) NR_CASE(32, 32, 32) NR_CASE(32, 64, 64) NR_CASE(32, 64, 16)
   NR_CASE(64, 32, 32) NR_CASE(64, 64, 64) NR_CASE(64, 16, 16) NR_CASE(64, 64, 32)
   NR_CASE(32, 16, 16)
@@ -553,18 +554,29 @@ int dispatch(const AttnArgs& g, int dk, int dv, bool bwd, hipStream_t s) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// nseq is the grid's x extent and heads (or heads / 2) its y extent; nr_mask_at reads any code past
+// NR_MASK_F32 as float32, so an unknown one is refused here
+bool sizes_ok(int64_t nseq, int L, int heads, int mask_dtype) {
+  return L >= 1 && L <= 64 && heads >= 1 && heads <= 65535 && nseq >= 0 && nseq <= INT32_MAX &&
+         mask_dtype >= NR_MASK_U8 && mask_dtype <= NR_MASK_F32;
+}
+
 }  // namespace
 
 extern "C" int nr_mha_attn_fwd(const float* qk, int64_t ld_qk, const float* v, int64_t ld_v,
                                const int64_t* rows, const void* mask, int32_t mask_dtype, int64_t nseq, int32_t L,
                                int32_t heads, int32_t dk, int32_t dv, float scale, float* out,
                                int64_t ld_out, hipStream_t stream) {
-  if (L < 1 || L > 64 || heads < 1) return NR_EINVAL(0);
+  if (!sizes_ok(nseq, L, heads, mask_dtype)) return NR_EINVAL(0);
   if (!qk || !v || !mask || !out) return NR_EINVAL(1);
-  if ((ld_qk | ld_v | ld_out) & 3 || !aligned16(qk) || !aligned16(v) || !aligned16(out)) return NR_EINVAL(2);
-  if (nseq == 0) return NR_OK;
+  const int64_t nk = (int64_t)heads * dk, nv = (int64_t)heads * dv;
+  if ((ld_qk | ld_v | ld_out) & 3 || !aligned16(qk) || !aligned16(v) || !aligned16(out) || ld_qk < nk || ld_v < nv ||
+      ld_out < nv)
+    return NR_EINVAL(2);
   AttnArgs g{qk, ld_qk, v, ld_v, mask, mask_dtype, nseq, L, heads, scale,
              nullptr, 0, out, ld_out, nullptr, 0, rows};
+  if (const int rc = dispatch(g, dk, dv, false, stream, true)) return rc;
+  if (nseq == 0) return NR_OK;
   return dispatch(g, dk, dv, false, stream);
 }
 
@@ -574,14 +586,17 @@ extern "C" int nr_mha_attn_bwd(const float* qk, int64_t ld_qk, const float* v, i
                                const float* dout, int64_t ld_dout, float* dqk, int64_t ld_dqk,
                                float* dvout, int64_t ld_dv, float* dbias_k, float* dbias_v,
                                hipStream_t stream) {
-  if (L < 1 || L > 64 || heads < 1) return NR_EINVAL(0);
+  if (!sizes_ok(nseq, L, heads, mask_dtype)) return NR_EINVAL(0);
   if (!qk || !v || !mask || !dout || !dqk || !dvout) return NR_EINVAL(1);
+  const int64_t nk = (int64_t)heads * dk, nv = (int64_t)heads * dv;
   if ((ld_qk | ld_v | ld_dout | ld_dqk | ld_dv) & 3 || !aligned16(qk) || !aligned16(v) ||
-      !aligned16(dout) || !aligned16(dqk) || !aligned16(dvout))
+      !aligned16(dout) || !aligned16(dqk) || !aligned16(dvout) || ld_qk < nk || ld_dqk < nk || ld_v < nv ||
+      ld_dout < nv || ld_dv < nv)
     return NR_EINVAL(2);
-  if (nseq == 0) return NR_OK;
   if ((dbias_k == nullptr) != (dbias_v == nullptr)) return NR_EINVAL(3);
   AttnArgs g{qk, ld_qk, v, ld_v, mask, mask_dtype, nseq, L, heads, scale,
              dout, ld_dout, dqk, ld_dqk, dvout, ld_dv, nullptr, dbias_k, dbias_v};
+  if (const int rc = dispatch(g, dk, dv, true, stream, true)) return rc;
+  if (nseq == 0) return NR_OK;
   return dispatch(g, dk, dv, true, stream);
 }

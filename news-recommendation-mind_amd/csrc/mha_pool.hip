@@ -1413,27 +1413,32 @@ extern "C" int nr_mha_user_pool_fwd(const float* y, int64_t ldy, int64_t y_rows,
                                     const void* mask, int32_t mask_dtype, int64_t nseq, int32_t L, int32_t heads,
                                     int32_t dk, int32_t dv, const float* q, float* out, int64_t ldo, int32_t prec,
                                     hipStream_t stream) {
-  if (L < 1 || L > 64 || heads < 1 || heads > 12) return NR_EINVAL(0);
+  if (L < 1 || L > 64 || heads < 1 || heads > 12 || nseq < 0 || nseq > INT32_MAX || mask_dtype < NR_MASK_U8 ||
+      mask_dtype > NR_MASK_F32)
+    return NR_EINVAL(0);
   if (y_rows < 1 || y_rows * ldy * 4 >= ((int64_t)1 << 32)) return NR_EINVAL(5);   // 32-bit row byte offsets
   if (prec != NR_GEMM_F32 && prec != NR_GEMM_BF16X6 && prec != NR_GEMM_BF16) return NR_EINVAL(4);
   if (!y || !mask || !q || !out) return NR_EINVAL(1);
   if ((ldy & 3) || !al16(y) || ldy < (int64_t)heads * (dk + dv)) return NR_EINVAL(2);
   if (ldo < (int64_t)heads * dv) return NR_EINVAL(3);
+  // the geometry is checked before the empty batch returns, so nseq = 0 reports the same codes
+  const int nh64 = heads * dv / 64;
+  if ((heads * dv) % 64) return NR_EINVAL(9);
+  // O [L][H + 1] stays in LDS: at H = 768 that caps L at 53 (the caller falls back to the two-launch
+  // path, kernels.mha_user_pool_supported)
+  if (user_pool_smem(heads * dv, L) > NR_MAX_LDS) return NR_EINVAL(10);
+  const int geom = dk == 32 && dv == 32 && nh64 == 6 ? 1 : dk == 64 && dv == 32 && nh64 == 6 ? 2 :
+                   dk == 64 && dv == 64 && nh64 == 12 ? 3 : 0;
+  if (!geom) return NR_EINVAL(8);
   if (nseq == 0) return NR_OK;
   MPArgs g{};
   g.y = y; g.ldy = ldy; g.yrows = yrows; g.mask = mask; g.mask_dt = mask_dtype; g.nseq = nseq; g.L = L;
   g.heads = heads; g.scale_attn = 1.0f / sqrtf((float)dk); g.scale_pool = 1.0f / sqrtf((float)(heads * dv));
   g.q = q; g.news = out; g.ldn = ldo;
   g.np = prec == NR_GEMM_BF16X6 ? 3 : prec == NR_GEMM_BF16 ? 1 : 0;
-  const int nh64 = heads * dv / 64;
-  if ((heads * dv) % 64) return NR_EINVAL(9);
-  // O [L][H + 1] stays in LDS: at H = 768 that caps L at 53 (the caller falls back to the two-launch
-  // path, kernels.mha_user_pool_supported)
-  if (user_pool_smem(heads * dv, L) > NR_MAX_LDS) return NR_EINVAL(10);
-  if (dk == 32 && dv == 32 && nh64 == 6) return launch_user_pool<32, 32, 6>(g, stream);
-  if (dk == 64 && dv == 32 && nh64 == 6) return launch_user_pool<64, 32, 6>(g, stream);
-  if (dk == 64 && dv == 64 && nh64 == 12) return launch_user_pool<64, 64, 12>(g, stream);
-  return NR_EINVAL(8);
+  if (geom == 1) return launch_user_pool<32, 32, 6>(g, stream);
+  if (geom == 2) return launch_user_pool<64, 32, 6>(g, stream);
+  return launch_user_pool<64, 64, 12>(g, stream);
 }
 
 extern "C" int nr_mha_pool_bwd(const float* y, int64_t ldy, const int64_t* yrows, const void* mask,
