@@ -292,7 +292,10 @@ int nr_cnn_unpack_grads(const float* dw3t, const float* dwqp, const float* dbqp,
  * 32 up to 160, L <= 32.  prec: enum nr_gemm_precision of the key products.  news [nseq][Hp]
  * (ldn >= Hp), probs [nseq*L].  kout (optional, [nseq*L][ldk >= Hp], ldk % 4 == 0, 16-B aligned,
  * L * ldk * 4 < 2^31): K
- * stored for the backward (which then skips the key recompute); NULL keeps the key projection on chip. */
+ * stored for the backward (which then skips the key recompute); NULL keeps the key projection on chip.
+ * Checked in this order, all before nseq == 0 returns 0 without a launch or a store: -1000 Hp, L (1 .. 32),
+ * qn (1 .. Hp), nseq < 0, ldc < Hp or ldc % 4, ldn < Hp; -1001 a NULL C, wq, bq, q, mask, news or probs;
+ * -1002 C or wq not 16-B aligned; -1003 a kout that breaks one of its conditions above. */
 int nr_cnn_keypool_fwd(const float* C, int64_t ldc, const float* wq, const float* bq, const float* q, int32_t qn,
                        const void* mask, int32_t mask_dtype, int64_t nseq, int32_t L, int32_t Hp, float scale,
                        int32_t prec, float* news, int64_t ldn, float* probs, float* kout, int64_t ldk,
@@ -303,7 +306,13 @@ int nr_cnn_keypool_fwd(const float* C, int64_t ldc, const float* wq, const float
  * Σ_t dc[t] -- all STORED (not accumulated), summed deterministically over per-workgroup partials in
  * ws (nr_cnn_keypool_workspace(nseq, Hp) floats).  kin (optional): the forward's kout -- K is read
  * instead of recomputed.  Replaces the reference's autograd through CNN.py:46 + Attention.py:22-29
- * and the ReLU of CNN.py:42. */
+ * and the ReLU of CNN.py:42.  dnews [nseq][lddn >= qn] and dz [T][lddz >= H] at any alignment, dc with any
+ * lddc >= Hp (columns H .. Hp of dc, rows and columns past H of dwq and dbq past H are stored as zeros).
+ * nseq == 0 still launches: dwq, dbq, dq and dconv_b are stored as zeros (dc has no rows).  Checked in this
+ * order: -1000 Hp, L, qn as in the forward, H (1 .. Hp), nseq < 0, ldc, lddn < qn, lddc < Hp, a dz with
+ * lddz < H; -1001 a NULL C, wq, bq, q, probs, dnews, dc, dwq, dbq, dq, dconv_b or ws; -1002 C or wq not 16-B
+ * aligned; -1004 a kin with ldk < Hp; -1003 ws_floats below nr_cnn_keypool_workspace(nseq, Hp), which is
+ * (min(max(nseq, 1), CUs of the device) + 8) * (Hp * Hp + 3 * Hp), or -1 for nseq < 0 or a bad Hp. */
 int64_t nr_cnn_keypool_workspace(int64_t nseq, int32_t Hp);
 int nr_cnn_keypool_bwd(const float* C, int64_t ldc, const float* wq, const float* bq, const float* q, int32_t qn,
                        int64_t nseq, int32_t L, int32_t Hp, int32_t H, float scale, int32_t prec,
@@ -463,14 +472,18 @@ int nr_attn_pool_bwd(const float* x, int64_t ldx, const float* key, int64_t ldk,
  * (Pooling.py:22-24).  D <= 1024, L <= 64; the row matrices (x, key, out, dx, dk, dz) 16-B aligned with
  * ld % 4 == 0 and ld >= D; q (and each dout row) hold qn <= D valid floats, any alignment, features
  * past qn taken as zero (a zero-padded row width D > qn then pools exact zeros there).  Saves
- * probs [nseq*L]. */
+ * probs [nseq*L].  Checked in this order, all before nseq == 0 returns 0 without a launch: -1000 L (1 .. 64),
+ * D (1 .. 1024), qn (1 .. D), nseq < 0, a bad ld, and x or key not 16-B aligned; -1001 a NULL x, q, mask, out
+ * or probs; -1002 out not 16-B aligned. */
 int nr_seq_pool_fwd(const float* x, int64_t ldx, const float* key, int64_t ldk, const float* q, int32_t qn,
                     const void* mask, int32_t mask_dtype, int64_t nseq, int32_t L, int32_t D, float scale,
                     float* out, int64_t ldo, float* probs, hipStream_t stream);
 
 /* Backward of nr_seq_pool_fwd: dx = p dout (+ ds q when tied) (+ dz), dk = ds q (* (1 - K²) when
  * key_tanh) for a separate key; ATOMICALLY ACCUMULATES dq[0 .. qn) (one add per feature per
- * workgroup). */
+ * workgroup).  dout [nseq][lddo >= qn] at any alignment; mask is required but not read (probs carries it).
+ * Checked as the forward: -1000 also lddo < qn and a bad lddx, lddz (with dz) or lddk (with key); -1001 a
+ * NULL x, q, mask, probs, dout, dx or dq, or a key without dk; -1002 dx, dz or dk not 16-B aligned. */
 int nr_seq_pool_bwd(const float* x, int64_t ldx, const float* key, int64_t ldk, const float* q, int32_t qn,
                     const void* mask, int32_t mask_dtype, int64_t nseq, int32_t L, int32_t D, float scale,
                     const float* probs, const float* dout, int64_t lddo, const float* dz, int64_t lddz,
