@@ -1093,6 +1093,41 @@ int nr_sha_attn_bwd(const float* qkv, int64_t ldq, int64_t koff, int64_t voff, c
                     uint64_t seed, uint64_t offset, const uint64_t* rng, const float* probs,
                     const float* dctx, int64_t ldd, float* dqkv, int64_t lddq, hipStream_t stream);
 
+/* ------------------------------------------------ PLM synthesizer tower (`-b synthesizer`)
+ * The dense-synthesizer attention core of models/Modules/Synthesizer.py's BertSelfAttention: the
+ * scores are a two-layer MLP over each token of the value projection, not q . k.  No mask (pad tokens
+ * attend and are attended to), no heads, no 1/sqrt(d) scale, no dropout.  For nseq titles of L tokens,
+ * with hv = value_fn(x) rows [nseq*L][D] (ld ldh), w1 [L][D] (ld ldw1), b1 [L], w2 [L][L] contiguous,
+ * b2 [L]:
+ *   a1[s*L+i][m]  = max(hv_i . w1_m + b1[m], 0)                         [nseq*L][lda], columns < L
+ *   a2[i][j]      = sum_m a1[i][m] w2[j][m] + b2[j]
+ *   probs[s][i][j] = softmax_j(a2[i][j])   over all L positions         [nseq][L][L] contiguous
+ *   ctx[s*L+i]    = sum_j probs[s][i][j] hv_j                           [nseq*L][D], ld ldc
+ * Every element of a1 (columns < L), probs and ctx is stored; the pad columns [L, lda) of a1 are left
+ * alone.  One workgroup per title, D walked in chunks of 64 columns through LDS; exact-f32 VALU fma
+ * chains, fp32 softmax with the row maximum subtracted; no atomics, two calls give the same bits.
+ * 1 <= L <= 64, 4 <= D <= 1024, D % 4 == 0; lda >= L (the caller may pad it to a multiple of 4);
+ * hv, w1, ctx (and dctx, dhv below) 16-B aligned with ld % 4 == 0 and ld >= D; w2, b1, b2, a1, probs
+ * (and da1, da2 below) 4-B aligned.
+ * Errors (before any HIP call, sizes before pointers): -1000 a size or ld outside the above, nseq < 0
+ * or > 2^31 - 1, or a misaligned operand; -1001 any pointer but stream NULL.  nseq == 0 returns 0
+ * without a launch. */
+int nr_synth_attn_fwd(const float* hv, int64_t ldh, const float* w1, int64_t ldw1, const float* b1,
+                      const float* w2, const float* b2, int64_t nseq, int32_t L, int32_t D, float* a1,
+                      int64_t lda, float* probs, float* ctx, int64_t ldc, hipStream_t stream);
+
+/* Backward of nr_synth_attn_fwd from its saved a1 and probs, given dctx [nseq*L][D] (ld ldd).  Per title:
+ *   dP  = dctx hv^T,  dA2 = P * (dP - rowsum(dP * P)),  dA1 = (dA2 w2) * (a1 > 0)   (the STORED a1)
+ *   dhv = P^T dctx + dA1 w1
+ * da1, da2 [nseq*L][lda] (columns < L; pad columns left alone) and dhv [nseq*L][D] (ld lddh): every
+ * element is stored, zeros included.  The sums over titles (dW1 = dA1^T hv, db1, dW2 = dA2^T a1, db2) are
+ * the caller's, through nr_gemm_f32 / nr_colsum on da1, da2, a1 and hv.  No atomics.
+ * Errors: as the forward (-1001 for any NULL of hv, w1, w2, a1, probs, dctx, da1, da2, dhv). */
+int nr_synth_attn_bwd(const float* hv, int64_t ldh, const float* w1, int64_t ldw1, const float* w2,
+                      const float* a1, int64_t lda, const float* probs, const float* dctx, int64_t ldd,
+                      int64_t nseq, int32_t L, int32_t D, float* da1, float* da2, float* dhv, int64_t lddh,
+                      hipStream_t stream);
+
 /* dx = dy * (1 - y^2): the pooler's tanh backward (BertPooler). */
 int nr_tanh_bwd(const float* y, int64_t ldy, const float* dy, int64_t lddy, int64_t rows, int32_t cols,
                 float* dx, int64_t lddx, hipStream_t stream);

@@ -179,6 +179,10 @@ _SIGS = {
                         c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "nr_sha_attn_bwd": [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i32, c_i64, c_i32, c_i32, c_f32, c_f32, c_u64, c_u64,
                         c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr],
+    "nr_synth_attn_fwd": [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_i64, c_ptr,
+                          c_ptr, c_i64, c_ptr],
+    "nr_synth_attn_bwd": [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_i32, c_i32,
+                          c_ptr, c_ptr, c_ptr, c_i64, c_ptr],
     "nr_tanh_bwd": [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr],
     "nr_adam_multi": [ctypes.POINTER(nr_adam_tensor), c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
     "nr_adam_multi_step": [ctypes.POINTER(nr_adam_tensor), c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr,

@@ -19,6 +19,14 @@ and the position ids are per segment).  Per layer:
   G   = gelu(h1 Wiᵀ + bi)                 nr_gemm_f32, NR_EPI_STORE_GELU (pre-activation kept)
   h2  = LN(Dropout(G Wo2ᵀ + bo2) + h1)    nr_gemm_f32 + nr_bert_add_ln_fwd
 and the pooler is tanh(h[CLS] Wpᵀ + bp): one gather-operand GEMM with a tanh epilogue.
+
+``BertConfig(attention_type="synthesizer", signal_length=L)`` is PLM's ``-b synthesizer`` tower
+(models/PLM.py:37-47, models/Modules/Synthesizer.py): the same model with the first two lines replaced by
+the dense synthesizer, whose scores are a two-layer MLP over each token (no mask, no heads, no dropout on
+the probabilities):
+
+  hv  = x Wvᵀ + bv                        nr_gemm_f32 (value_fn)
+  ctx = softmax(relu(hv W1ᵀ + b1) W2ᵀ + b2) hv      nr_synth_attn_fwd, per title of exactly L tokens
 """
 from collections import namedtuple
 
@@ -35,7 +43,8 @@ class BertConfig:
 
     def __init__(self, vocab_size=30522, hidden_size=768, num_hidden_layers=12, num_attention_heads=12,
                  intermediate_size=3072, max_position_embeddings=512, type_vocab_size=2, layer_norm_eps=1e-12,
-                 hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, pad_token_id=0, initializer_range=0.02):
+                 hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, pad_token_id=0, initializer_range=0.02,
+                 attention_type="bert", signal_length=None):
         self.vocab_size = vocab_size
         self.hidden_size = hidden_size
         self.num_hidden_layers = num_hidden_layers
@@ -48,6 +57,8 @@ class BertConfig:
         self.attention_probs_dropout_prob = attention_probs_dropout_prob
         self.pad_token_id = pad_token_id
         self.initializer_range = initializer_range
+        self.attention_type = attention_type      # "bert" or "synthesizer" (PLM.py:37-47)
+        self.signal_length = signal_length        # the synthesizer's title length (its score MLP's width)
 
 
 BertOutput = namedtuple("BertOutput", ["last_hidden_state", "pooler_output"])
@@ -66,6 +77,12 @@ class BertEmbeddings(nn.Module):
 class BertSelfAttention(nn.Module):
     def __init__(self, c):
         super().__init__()
+        if c.attention_type == "synthesizer":     # Synthesizer.py:14-21
+            self.dense = nn.Sequential(nn.Linear(c.hidden_size, c.signal_length), nn.ReLU(),
+                                       nn.Linear(c.signal_length, c.signal_length))
+            self.value_fn = nn.Linear(c.hidden_size, c.hidden_size)
+            self.dropout = nn.Dropout(c.attention_probs_dropout_prob)
+            return
         self.query = nn.Linear(c.hidden_size, c.hidden_size)
         self.key = nn.Linear(c.hidden_size, c.hidden_size)
         self.value = nn.Linear(c.hidden_size, c.hidden_size)
@@ -156,6 +173,8 @@ class BertFn(torch.autograd.Function):
         cls_idx = torch.cat(cls)
         p_h = c.hidden_dropout_prob if drop is not None else 0.0
         p_a = c.attention_probs_dropout_prob if drop is not None else 0.0
+        synth = c.attention_type == "synthesizer"
+        SL = c.signal_length
 
         def dsite(k):
             if drop is None:
@@ -180,20 +199,35 @@ class BertFn(torch.autograd.Function):
         saved, keeps_all = [], []
         for li, w in enumerate(lp):
             wq, bq, wk, bk, wv, bv, wo, bo, l1w, l1b, wi, bi, wo2, bo2, l2w, l2b = w
-            wqkv = torch.cat([wq, wk, wv], 0)
-            bqkv = torch.cat([bq, bk, bv], 0)
-            qkv = _empty(T, 3 * H, word)
-            K.gemm(T, 3 * H, H, K.operand(x, L.KCONTIG), K.operand(wqkv, L.KCONTIG), qkv, bias=bqkv)
-            cx = _empty(T, H, word)
-            ml = torch.empty(T * heads * 2, device=dev)
-            # the bf16-MFMA attention keeps its dropout bits for the backward (instead of re-hashing
-            # every probability's counter twice there): ~12 MB per layer for B = 32's user sequences
-            keeps = [K.bert_attn_keep_buffer(s.nseq, s.L, heads, dev)
-                     if p_a > 0 and ctx.prec != L.GEMM_F32 else None for s in segs]
-            for s, r0, kp in zip(segs, r0s, keeps):
-                n = s.nseq * s.L
-                K.bert_attn_fwd(qkv[r0:r0 + n], heads, s.mask, s.nseq, s.L, cx[r0:r0 + n],
-                                ml[r0 * heads * 2:(r0 + n) * heads * 2], keep=kp, **dsite_seg(1 + 3 * li, p_a, r0))
+            if synth:
+                # the six attention tensors sit in the Q/K/V slots: dense.0, dense.2, value_fn
+                w1, b1, w2, b2 = wq, bq, wk, bk
+                wqkv = _empty(T, H, word)                       # hv (the slot of the fused weight)
+                K.gemm(T, H, H, K.operand(x, L.KCONTIG), K.operand(wv, L.KCONTIG), wqkv, bias=bv)
+                cx = _empty(T, H, word)
+                qkv = _empty(T, SL, word)                       # a1, kept for the backward's gate
+                ml = torch.empty(T * SL, device=dev)            # the probabilities [n, L, L] of every segment
+                keeps = None
+                for s, r0 in zip(segs, r0s):
+                    n = s.nseq * s.L
+                    K.synth_attn_fwd(wqkv[r0:r0 + n], w1, b1, w2, b2, s.nseq, SL, H, qkv[r0:r0 + n],
+                                     ml[r0 * SL:(r0 + n) * SL], cx[r0:r0 + n])
+            else:
+                wqkv = torch.cat([wq, wk, wv], 0)
+                bqkv = torch.cat([bq, bk, bv], 0)
+                qkv = _empty(T, 3 * H, word)
+                K.gemm(T, 3 * H, H, K.operand(x, L.KCONTIG), K.operand(wqkv, L.KCONTIG), qkv, bias=bqkv)
+                cx = _empty(T, H, word)
+                ml = torch.empty(T * heads * 2, device=dev)
+                # the bf16-MFMA attention keeps its dropout bits for the backward (instead of re-hashing
+                # every probability's counter twice there): ~12 MB per layer for B = 32's user sequences
+                keeps = [K.bert_attn_keep_buffer(s.nseq, s.L, heads, dev)
+                         if p_a > 0 and ctx.prec != L.GEMM_F32 else None for s in segs]
+                for s, r0, kp in zip(segs, r0s, keeps):
+                    n = s.nseq * s.L
+                    K.bert_attn_fwd(qkv[r0:r0 + n], heads, s.mask, s.nseq, s.L, cx[r0:r0 + n],
+                                    ml[r0 * heads * 2:(r0 + n) * heads * 2], keep=kp,
+                                    **dsite_seg(1 + 3 * li, p_a, r0))
             a = _empty(T, H, word)
             K.gemm(T, H, H, K.operand(cx, L.KCONTIG), K.operand(wo, L.KCONTIG), a, bias=bo)
             h1 = _empty(T, H, word)
@@ -240,6 +274,8 @@ class BertFn(torch.autograd.Function):
         S = pooled.shape[0]
         segs, r0s, dsite_seg = ctx.segs, ctx.r0s, ctx.dsite_seg
         p_h, p_a = ctx.p
+        synth = c.attention_type == "synthesizer"
+        SL = c.signal_length
         grads = [None] * npar
         z = lambda t: torch.zeros_like(t)   # noqa: E731
 
@@ -260,10 +296,14 @@ class BertFn(torch.autograd.Function):
         for li in reversed(range(nl)):
             x, wqkv, qkv, cx, ml, a, st1, h1, U, G, o, st2 = saved[12 * li: 12 * (li + 1)]
             wq, bq, wk, bk, wv, bv, wo, bo, l1w, l1b, wi, bi, wo2, bo2, l2w, l2b = lp[li]
-            # one fill for all 16 gradients of the layer; Q/K/V weight and bias grads are slices of the
-            # fused [3H, H] / [3H] wgrad outputs
-            dwqkv, dbqkv, *grest = _zeros_views(dev, (3 * H, H), (3 * H,), *[tuple(t.shape) for t in lp[li][6:]])
-            g = [dwqkv[:H], dbqkv[:H], dwqkv[H:2 * H], dbqkv[H:2 * H], dwqkv[2 * H:], dbqkv[2 * H:]] + grest
+            if synth:
+                g = _zeros_views(dev, *[tuple(t.shape) for t in lp[li]])
+            else:
+                # one fill for all 16 gradients of the layer; Q/K/V weight and bias grads are slices of the
+                # fused [3H, H] / [3H] wgrad outputs
+                dwqkv, dbqkv, *grest = _zeros_views(dev, (3 * H, H), (3 * H,),
+                                                    *[tuple(t.shape) for t in lp[li][6:]])
+                g = [dwqkv[:H], dbqkv[:H], dwqkv[H:2 * H], dbqkv[H:2 * H], dwqkv[2 * H:], dbqkv[2 * H:]] + grest
             dh1 = _empty(T, H, word)
             do = _empty(T, H, word)
             K.bert_add_ln_bwd(o, h1, l2w, st2, dh, dh1, do, g[14], g[15], **dsite_seg(3 + 3 * li, p_h, 0))
@@ -279,14 +319,30 @@ class BertFn(torch.autograd.Function):
             dcx = _empty(T, H, word)
             K.gemm(T, H, H, K.operand(da, L.KCONTIG), K.operand(wo, L.MNCONTIG), dcx)
             _proj_wgrad(da, K.operand(cx, L.MNCONTIG), g[6], g[7], T)
-            dqkv = _empty(T, 3 * H, word)
-            for s, r0, kp in zip(segs, r0s, ctx.keeps[li]):
-                n = s.nseq * s.L
-                K.bert_attn_bwd(qkv[r0:r0 + n], heads, s.mask, s.nseq, s.L, cx[r0:r0 + n],
-                                ml[r0 * heads * 2:(r0 + n) * heads * 2], dcx[r0:r0 + n], dqkv[r0:r0 + n],
-                                keep=kp, **dsite_seg(1 + 3 * li, p_a, r0))
-            K.gemm(T, H, 3 * H, K.operand(dqkv, L.KCONTIG), K.operand(wqkv, L.MNCONTIG), dx, epilogue=L.EPI_ACCUM)
-            _proj_wgrad(dqkv, K.operand(x, L.MNCONTIG), dwqkv, dbqkv, T)
+            if synth:
+                hv, a1, probs, w1, w2 = wqkv, qkv, ml, wq, wk
+                da1 = _empty(T, SL, word)
+                da2 = _empty(T, SL, word)
+                dhv = _empty(T, H, word)
+                for s, r0 in zip(segs, r0s):
+                    n = s.nseq * s.L
+                    K.synth_attn_bwd(hv[r0:r0 + n], w1, w2, a1[r0:r0 + n], probs[r0 * SL:(r0 + n) * SL],
+                                     dcx[r0:r0 + n], s.nseq, SL, H, da1[r0:r0 + n], da2[r0:r0 + n], dhv[r0:r0 + n])
+                # the sums over titles take the project's one weight-gradient path
+                _proj_wgrad(da2, K.operand(a1, L.MNCONTIG), g[2], g[3], T)
+                _proj_wgrad(da1, K.operand(hv, L.MNCONTIG), g[0], g[1], T)
+                K.gemm(T, H, H, K.operand(dhv, L.KCONTIG), K.operand(wv, L.MNCONTIG), dx, epilogue=L.EPI_ACCUM)
+                _proj_wgrad(dhv, K.operand(x, L.MNCONTIG), g[4], g[5], T)
+            else:
+                dqkv = _empty(T, 3 * H, word)
+                for s, r0, kp in zip(segs, r0s, ctx.keeps[li]):
+                    n = s.nseq * s.L
+                    K.bert_attn_bwd(qkv[r0:r0 + n], heads, s.mask, s.nseq, s.L, cx[r0:r0 + n],
+                                    ml[r0 * heads * 2:(r0 + n) * heads * 2], dcx[r0:r0 + n], dqkv[r0:r0 + n],
+                                    keep=kp, **dsite_seg(1 + 3 * li, p_a, r0))
+                K.gemm(T, H, 3 * H, K.operand(dqkv, L.KCONTIG), K.operand(wqkv, L.MNCONTIG), dx,
+                       epilogue=L.EPI_ACCUM)
+                _proj_wgrad(dqkv, K.operand(x, L.MNCONTIG), dwqkv, dbqkv, T)
             for k in range(16):
                 grads[5 + 16 * li + k] = g[k]
             dh = dx
@@ -317,6 +373,12 @@ class BertModel(nn.Module):
         super().__init__()
         self.config = config or BertConfig()
         c = self.config
+        if c.attention_type not in ("bert", "synthesizer"):
+            raise ValueError("attention_type must be 'bert' or 'synthesizer' (got %r)" % (c.attention_type,))
+        if c.attention_type == "synthesizer" and not (isinstance(c.signal_length, int)
+                                                      and 1 <= c.signal_length <= K.SHA_MAX_L):
+            raise ValueError("the synthesizer tower needs signal_length in [1, %d] (got %r)"
+                             % (K.SHA_MAX_L, c.signal_length))
         if c.hidden_size % c.num_attention_heads or c.hidden_size // c.num_attention_heads != 64:
             raise ValueError("the HIP attention kernels take 64-dim heads (hidden %d / %d heads)"
                              % (c.hidden_size, c.num_attention_heads))
@@ -329,10 +391,18 @@ class BertModel(nn.Module):
 
     def _init_weights(self):
         """BertPreTrainedModel._init_weights: normal(0, 0.02) weights, zero biases, padding row 0,
-        LayerNorm (1, 0)."""
+        LayerNorm (1, 0).  The synthesizer's dense.0 / dense.2 / value_fn keep nn.Linear's default init: the
+        reference swaps them in after BertModel's own init and loads the checkpoint with strict=False
+        (PLM.py:45-47)."""
         r = self.config.initializer_range
+        keep = set()
+        if self.config.attention_type == "synthesizer":
+            for l in self.encoder.layer:
+                keep.update(m for m in l.attention.self.modules() if isinstance(m, nn.Linear))
         with torch.no_grad():
             for m in self.modules():
+                if m in keep:
+                    continue
                 if isinstance(m, nn.Linear):
                     m.weight.normal_(0.0, r)
                     m.bias.zero_()
@@ -348,10 +418,15 @@ class BertModel(nn.Module):
         e = self.embeddings
         ps = [e.word_embeddings.weight, e.position_embeddings.weight, e.token_type_embeddings.weight,
               e.LayerNorm.weight, e.LayerNorm.bias]
+        synth = self.config.attention_type == "synthesizer"
         for l in self.encoder.layer:
             a = l.attention
-            ps += [a.self.query.weight, a.self.query.bias, a.self.key.weight, a.self.key.bias,
-                   a.self.value.weight, a.self.value.bias, a.output.dense.weight, a.output.dense.bias,
+            # 16 tensors per layer either way: the synthesizer's six take the Q/K/V slots
+            att = ([a.self.dense[0].weight, a.self.dense[0].bias, a.self.dense[2].weight, a.self.dense[2].bias,
+                    a.self.value_fn.weight, a.self.value_fn.bias] if synth else
+                   [a.self.query.weight, a.self.query.bias, a.self.key.weight, a.self.key.bias,
+                    a.self.value.weight, a.self.value.bias])
+            ps += att + [a.output.dense.weight, a.output.dense.bias,
                    a.output.LayerNorm.weight, a.output.LayerNorm.bias, l.intermediate.dense.weight,
                    l.intermediate.dense.bias, l.output.dense.weight, l.output.dense.bias,
                    l.output.LayerNorm.weight, l.output.LayerNorm.bias]
@@ -366,7 +441,8 @@ class BertModel(nn.Module):
         # counter ranges of the 1 + 3 x layers sites (attention: per (seq, head) keys, q*L + k), taken
         # as ONE snapshot (one nr_rng_take launch per step instead of 37); a site's kernels add its
         # start inside the range to the snapshot's device offset -- the same counters, hence masks,
-        # as one take per site
+        # as one take per site.  The synthesizer has no probability dropout: its attention site stays in the
+        # layout unused, so the hidden-dropout masks are the bert tower's function of (seed, offset)
         sizes = [T * H] + [T * 64, T * H, T * H] * c.num_hidden_layers
         seed, off, snap = self._rng.take(sum(sizes), device)
         sites, rel = [], 0
@@ -379,6 +455,12 @@ class BertModel(nn.Module):
         """[(input_ids [n, L], attention_mask [n, L]), ...] -> [BertOutput per segment] from ONE
         fused pass (every dense layer runs once over the rows of all segments)."""
         dev = self.embeddings.word_embeddings.weight.device
+        c = self.config
+        if c.attention_type == "synthesizer":
+            for ids, _ in segments:
+                if ids.shape[-1] != c.signal_length:
+                    raise ValueError("the synthesizer tower takes titles of signal_length = %d tokens (got %d)"
+                                     % (c.signal_length, ids.shape[-1]))
         segs = []
         for ids, mask in segments:
             L.require_gpu(ids.to(dev))

@@ -1321,6 +1321,60 @@ def sha_attn_bwd(qkv, mask, nseq, seq_len, D, probs, dctx, dqkv, koff=None, voff
            L.ptr(probs), L.ptr(dctx), dctx.stride(0), L.ptr(dqkv), dqkv.stride(0), L.stream_ptr(qkv))
 
 
+def _synth_check(hv, w1, w2, nseq, seq_len, D, who):
+    if nseq < 0 or not 1 <= seq_len <= SHA_MAX_L or not 4 <= D <= SHA_MAX_D or D % 4:
+        raise L.HipError("%s: needs nseq >= 0, 1 <= L <= %d, 4 <= D <= %d and D %% 4 == 0 (got %d, %d, %d)"
+                         % (who, SHA_MAX_L, SHA_MAX_D, nseq, seq_len, D))
+    _f32(hv, w1, w2)
+    _al(hv, who + " hv")
+    _al(w1, who + " w1")
+    _rows_ok(hv, nseq * seq_len, D, "hv")
+    _rows_ok(w1, seq_len, D, "w1")
+    if tuple(w2.shape) != (seq_len, seq_len) or not w2.is_contiguous():
+        raise L.HipError("%s: w2 must be a contiguous [L, L] matrix" % who)
+
+
+def _synth_acts(who, nseq, seq_len, *ts):
+    """a1 / da1 / da2: row-major [>= nseq*L, >= L] matrices of one shared leading dimension."""
+    for t in ts:
+        _rows_ok(t, nseq * seq_len, seq_len, who + " activations")
+    if len({t.stride(0) for t in ts}) != 1:
+        raise L.HipError("%s: a1, da1 and da2 must share one leading dimension" % who)
+    return ts[0].stride(0)
+
+
+def synth_attn_fwd(hv, w1, b1, w2, b2, nseq, seq_len, D, a1, probs, ctx):
+    """nr_synth_attn_fwd: the dense-synthesizer attention core on hv = value_fn(x) [T, D]: a1 [T, lda >= L]
+    (the MLP's hidden activation, kept for the backward's gate), probs (flat, nseq*L*L floats) and ctx [T, D]."""
+    _synth_check(hv, w1, w2, nseq, seq_len, D, "synth_attn_fwd")
+    _f32(b1, b2, a1, probs, ctx)
+    if b1.numel() != seq_len or b2.numel() != seq_len or not b1.is_contiguous() or not b2.is_contiguous():
+        raise L.HipError("synth_attn_fwd: b1 and b2 must hold L contiguous floats")
+    lda = _synth_acts("synth_attn_fwd", nseq, seq_len, a1)
+    _al(ctx, "synth_attn_fwd ctx")
+    _rows_ok(ctx, nseq * seq_len, D, "ctx")
+    if not probs.is_contiguous() or probs.numel() < nseq * seq_len * seq_len:
+        raise L.HipError("synth_attn_fwd: probs needs nseq*L*L contiguous floats")
+    L.call("nr_synth_attn_fwd", L.ptr(hv), hv.stride(0), L.ptr(w1), w1.stride(0), L.ptr(b1), L.ptr(w2), L.ptr(b2),
+           nseq, seq_len, D, L.ptr(a1), lda, L.ptr(probs), L.ptr(ctx), ctx.stride(0), L.stream_ptr(hv))
+
+
+def synth_attn_bwd(hv, w1, w2, a1, probs, dctx, nseq, seq_len, D, da1, da2, dhv):
+    """nr_synth_attn_bwd: dctx [T, D] -> da1, da2 [T, lda] (a1's leading dimension) and dhv [T, D], every
+    element stored; the weight gradients are the caller's GEMMs over da1 / da2."""
+    _synth_check(hv, w1, w2, nseq, seq_len, D, "synth_attn_bwd")
+    _f32(a1, probs, dctx, da1, da2, dhv)
+    lda = _synth_acts("synth_attn_bwd", nseq, seq_len, a1, da1, da2)
+    for t, n in ((dctx, "dctx"), (dhv, "dhv")):
+        _al(t, "synth_attn_bwd " + n)
+        _rows_ok(t, nseq * seq_len, D, n)
+    if not probs.is_contiguous() or probs.numel() < nseq * seq_len * seq_len:
+        raise L.HipError("synth_attn_bwd: probs needs nseq*L*L contiguous floats")
+    L.call("nr_synth_attn_bwd", L.ptr(hv), hv.stride(0), L.ptr(w1), w1.stride(0), L.ptr(w2), L.ptr(a1), lda,
+           L.ptr(probs), L.ptr(dctx), dctx.stride(0), nseq, seq_len, D, L.ptr(da1), L.ptr(da2), L.ptr(dhv),
+           dhv.stride(0), L.stream_ptr(hv))
+
+
 def tanh_bwd(y, dy, dx):
     _f32(y, dy, dx)
     rows, cols = y.shape

@@ -14,7 +14,7 @@ NEWS_NUM = {"demo": 42416, "small": 42416, "large": 72023, "whole": 72023}      
 class ManagerConfig:
     def __init__(self, encoderN="cnn", encoderU="lstm", hidden_dim=150, scale="large", mode="train",
                  device="cuda", dropout_p=0.2, head_num=12, his_size=50, signal_length=30, npratio=4,
-                 bert_dim=768, descend_history=False, user_num=None, lr=1e-4, bert_lr=6e-6):
+                 bert_dim=768, descend_history=False, user_num=None, lr=1e-4, bert_lr=6e-6, bert="bert"):
         self.scale = scale; self.mode = mode; self.npratio = npratio; self.cdd_size = npratio + 1
         self.impr_size = 2000; self.batch_size_news = 500
         self.his_size = his_size; self.signal_length = signal_length; self.device = device
@@ -23,6 +23,7 @@ class ManagerConfig:
         self.encoderN = encoderN; self.encoderU = encoderU
         self.user_num = USER_NUM[scale] if user_num is None else user_num
         self.lr = lr; self.bert_lr = bert_lr
+        self.bert = bert      # the PLM tower (-b): "bert" or "synthesizer"
 
     def get_user_num(self):
         return self.user_num

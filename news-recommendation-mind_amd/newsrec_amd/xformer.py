@@ -5,8 +5,13 @@ Both keep the reference's constructors (a ``manager``), attribute and parameter 
 (``encode_news``, ``encode_user``, ``forward`` via TwoTowerBaseModel).  ``forward`` runs the
 candidate titles and the user side through ONE fused BERT pass (``BertModel.encode_segments``).
 
-Out of scope: the reformer / longformer / bigbird / deberta / funnel /
-synthesizer / distill / newsbert variants (XFormer.py:19-41, PLM.py:20-78) — only ``bert``.
+``PLM`` also takes ``manager.bert == "synthesizer"`` (PLM.py:37-47): the same tower with the dense
+synthesizer in place of every layer's self-attention (``BertConfig(attention_type="synthesizer")``, titles
+of exactly ``manager.signal_length`` tokens).  ``XFormer`` refuses it: the reference builds none there, and
+its 501-token user sequence has no signal_length.
+
+Out of scope: the reformer / longformer / bigbird / deberta / funnel / distill /
+newsbert variants (XFormer.py:19-41, PLM.py:20-78).
 """
 import torch
 from torch import nn
@@ -18,14 +23,18 @@ from .twotower import TwoTowerBaseModel
 MAX_LENGTH = {"bert": (512, 10)}
 
 
-def _bert_for(manager, bert, bert_config):
+def _bert_for(manager, bert, bert_config, towers=("bert",)):
     name = getattr(manager, "bert", "bert")
-    if name != "bert":
-        raise NotImplementedError("only the 'bert' tower is built (got %r)" % name)
+    if name not in towers:
+        raise NotImplementedError("only the %s tower%s built here (got %r)"
+                                  % (" / ".join(repr(t) for t in towers), " is" if len(towers) == 1 else "s are", name))
     if bert is not None:
         return bert
     if bert_config is None:
-        bert_config = BertConfig(hidden_size=manager.bert_dim, num_attention_heads=manager.bert_dim // 64)
+        kw = {}
+        if name == "synthesizer":     # PLM.py:37-47: BERT-base with Synthesizer.py's self-attention in every layer
+            kw = dict(attention_type="synthesizer", signal_length=manager.signal_length)
+        bert_config = BertConfig(hidden_size=manager.bert_dim, num_attention_heads=manager.bert_dim // 64, **kw)
     return BertModel(bert_config)
 
 
@@ -44,8 +53,8 @@ class XFormer(TwoTowerBaseModel):
     def __init__(self, manager, bert=None, bert_config=None):
         super().__init__(manager)
         self.bert_name = getattr(manager, "bert", "bert")
+        self.bert = _bert_for(manager, bert, bert_config)     # refuses every tower but "bert"
         self.max_length, self.max_length_per_history = MAX_LENGTH[self.bert_name]
-        self.bert = _bert_for(manager, bert, bert_config)
         ub = _user_bias(manager)
         if ub is not None:
             self.userBias = ub
@@ -103,7 +112,7 @@ class PLM(TwoTowerBaseModel):
         ub = _user_bias(manager)
         if ub is not None:
             self.userBias = ub
-        self.bert = _bert_for(manager, bert, bert_config)
+        self.bert = _bert_for(manager, bert, bert_config, towers=("bert", "synthesizer"))
         manager.name = "__".join(["plm", getattr(manager, "bert", "bert"), manager.encoderU])
         self.name = manager.name
 
