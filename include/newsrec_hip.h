@@ -1128,6 +1128,62 @@ int nr_synth_attn_bwd(const float* hv, int64_t ldh, const float* w1, int64_t ldw
                       int64_t nseq, int32_t L, int32_t D, float* da1, float* da2, float* dhv, int64_t lddh,
                       hipStream_t stream);
 
+/* ------------------------------------------------ PLM DeBERTa tower (`-b deberta`)
+ * The disentangled self-attention core of transformers' DebertaModel (relative_attention, pos_att_type
+ * c2p | p2c, no talking heads).  For nseq titles of L tokens and `heads` heads of 64 dims: head h's q / k / v
+ * are the 64 columns at h * hstride + qoff / koff / voff of qkv rows [nseq*L][ldq] (DeBERTa's interleaved
+ * in_proj: hstride 192, offsets 0, 64, 128; a blocked projection: hstride 64, offsets 0, 64 heads,
+ * 128 heads); pk = pos_proj(rel) and pq = pos_q_proj(rel) are [2L][ldp] with head h at columns 64 h, rel
+ * being the 2L rows K - L .. K + L - 1 of rel_embeddings.  With delta(i, j) = i - j + L in [1, 2L - 1]:
+ *   S[i][j]        = scale * (q_i . k_j + q_i . pk[delta(i, j)] + k_j . pq[delta(i, j)])
+ *   probs[s][h][i] = softmax of S[i] over the keys with mask[s][j] != 0, exactly 0 at the others, when
+ *                    mask[s][i] != 0; 1 / L at every key when mask[s][i] == 0      [nseq][heads][L][L]
+ *   ctx[s*L+i]     = sum_j (probs[s][h][i][j] * keep / (1 - p_drop)) v_j   at columns 64 h, ld ldc
+ * probs is stored after the mask and before the dropout.  Dropout: key = nr_dropout_key(seed, offset) (or of
+ * the device pair rng with offset added), element index ((s * heads + h) * L + i) * L + j (mod 2^32).
+ * mask: [nseq, L] of enum nr_mask_dtype.  q and v carry their biases already; the caller supplies scale
+ * (DeBERTa: 1 / sqrt(3 * 64)).
+ * One workgroup per (title, head), the operands staged in LDS; a query's L position rows are read in place
+ * (the L x 2L products are never formed); exact-f32 VALU fma chains, fp32 softmax with the row maximum
+ * subtracted; no atomics, two calls give the same bits.
+ * 1 <= L <= 64, 1 <= heads <= 1024, nseq * heads <= 2^31 - 1; ldq % 4 == 0; hstride, qoff, koff, voff
+ * multiples of 4, offsets >= 0 and 64 or more apart, hstride >= 64, (heads - 1) hstride + the largest
+ * offset + 64 <= ldq (blocks of different heads must not overlap either: the caller's layout); ldp, ldc
+ * % 4 == 0 and >= 64 heads; qkv, pk, pq, ctx 16-B aligned; 0 <= p_drop < 1.
+ * Errors (before any HIP call): -1000 a size, offset, ld, p_drop or mask_dtype outside the above, a
+ * misaligned operand, or a launch the kernel's bounds (256 threads, 160 KB of LDS) do not admit; -1001 qkv,
+ * pk, pq, mask, probs or ctx NULL.  nseq == 0 returns 0 without a launch. */
+int nr_deb_attn_fwd(const float* qkv, int64_t ldq, int64_t hstride, int64_t qoff, int64_t koff, int64_t voff,
+                    const float* pk, const float* pq, int64_t ldp, const void* mask, int32_t mask_dtype,
+                    int64_t nseq, int32_t L, int32_t heads, float scale, float p_drop, uint64_t seed,
+                    uint64_t offset, const uint64_t* rng, float* probs, float* ctx, int64_t ldc,
+                    hipStream_t stream);
+
+/* Bytes of `work` nr_deb_attn_bwd needs: the [2][2L][64] partial sums of dpk / dpq of each of its
+ * min(nseq, max(1, 512 / heads)) x heads workgroups.  -1000 on sizes outside nr_deb_attn_fwd's. */
+int64_t nr_deb_attn_bwd_workspace(int64_t nseq, int32_t L, int32_t heads);
+
+/* Backward of nr_deb_attn_fwd from its saved probs and the same RNG triple, given dctx [nseq*L][ldd] (head
+ * h at columns 64 h).  With Pd = P * keep / (1 - p), dPd = dctx v^T, g = dPd * keep / (1 - p) and
+ * dS = scale * P * (g - rowsum(g * P)) for a query with mask != 0, 0 for the others:
+ *   dV = Pd^T dctx      dq_i = sum_j dS[i][j] (k_j + pk[delta(i, j)])
+ *                       dk_j = sum_i dS[i][j] (q_i + pq[delta(i, j)])
+ *   dpk[d] = sum over titles and (i, j) with delta(i, j) = d of dS[i][j] q_i;  dpq[d] likewise with k_j
+ * dq, dk, dv go to dqkv (ld lddq) at qkv's columns: every element of the three blocks of every head is
+ * stored, zeros included; other columns are left alone.  dpk, dpq [2L][lddp]: every element of the 64 heads
+ * columns is stored, row 0 (which no (i, j) indexes) as 0.  Workgroup (g, h) walks the titles g, g + G, ... of
+ * head h with its partial sums in registers, stores them in work, and a second kernel adds the G partials
+ * in ascending g: no atomics, two calls give the same bits.
+ * Errors: as the forward, with dctx, dqkv, dpk, dpq, work for ctx (16-B aligned; -1001 when NULL), lddq
+ * under ldq's rules, ldd and lddp % 4 == 0 and >= 64 heads, and -1000 for work_bytes below
+ * nr_deb_attn_bwd_workspace(nseq, L, heads).  nseq == 0 returns 0 without a launch or a store. */
+int nr_deb_attn_bwd(const float* qkv, int64_t ldq, int64_t hstride, int64_t qoff, int64_t koff, int64_t voff,
+                    const float* pk, const float* pq, int64_t ldp, const void* mask, int32_t mask_dtype,
+                    int64_t nseq, int32_t L, int32_t heads, float scale, float p_drop, uint64_t seed,
+                    uint64_t offset, const uint64_t* rng, const float* probs, const float* dctx, int64_t ldd,
+                    float* dqkv, int64_t lddq, float* dpk, float* dpq, int64_t lddp, float* work,
+                    int64_t work_bytes, hipStream_t stream);
+
 /* dx = dy * (1 - y^2): the pooler's tanh backward (BertPooler). */
 int nr_tanh_bwd(const float* y, int64_t ldy, const float* dy, int64_t lddy, int64_t rows, int32_t cols,
                 float* dx, int64_t lddx, hipStream_t stream);

@@ -183,6 +183,12 @@ _SIGS = {
                           c_ptr, c_i64, c_ptr],
     "nr_synth_attn_bwd": [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_i32, c_i32,
                           c_ptr, c_ptr, c_ptr, c_i64, c_ptr],
+    "nr_deb_attn_fwd": [c_ptr, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_i64, c_i32,
+                        c_i32, c_f32, c_f32, c_u64, c_u64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr],
+    "nr_deb_attn_bwd_workspace": [c_i64, c_i32, c_i32],
+    "nr_deb_attn_bwd": [c_ptr, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_i64, c_i32,
+                        c_i32, c_f32, c_f32, c_u64, c_u64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr,
+                        c_i64, c_ptr, c_i64, c_ptr],
     "nr_tanh_bwd": [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr],
     "nr_adam_multi": [ctypes.POINTER(nr_adam_tensor), c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
     "nr_adam_multi_step": [ctypes.POINTER(nr_adam_tensor), c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr,
@@ -198,7 +204,8 @@ _RESTYPES = {"nr_segment_rows_sum_workspace": c_i64, "nr_bert_attn_keep_words": 
              "nr_colsum_workspace": c_i64, "nr_score_nll_workspace": c_i64,
              "nr_gemm_splitk_workspace": c_i64, "nr_cnn_keypool_workspace": c_i64,
              "nr_topk_workspace": c_i64, "nr_grad_norm_workspace": c_i64, "nr_build_hash": ctypes.c_char_p,
-             "nr_bm25_build_workspace": c_i64, "nr_bm25_topk_workspace": c_i64}
+             "nr_bm25_build_workspace": c_i64, "nr_bm25_topk_workspace": c_i64,
+             "nr_deb_attn_bwd_workspace": c_i64}
 
 # enum nr_batch_flags / nr_metric_flags / nr_rank_flags, NR_RANK_MAX_GROUP
 BATCH_REVERSE_HISTORY, BATCH_SHUFFLE_POS, BATCH_CURSOR = 1, 2, 4

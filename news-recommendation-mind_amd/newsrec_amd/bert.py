@@ -148,6 +148,56 @@ class _Segment:
         self.mask = m if m.is_contiguous() else m.contiguous()
 
 
+def layer_tail_fwd(c, x, cx, w, drop1, drop2):
+    """The layer behind its attention core, shared by every tower (BertSelfOutput, BertIntermediate, BertOutput):
+    h1 = LN(Dropout(cx Woᵀ + bo) + x), G = gelu(h1 Wiᵀ + bi), h2 = LN(Dropout(G Wo2ᵀ + bo2) + h1).
+    w: the layer's last ten tensors; drop1 / drop2: the two dropout sites' keyword arguments.
+    -> (a, st1, h1, U, G, o, st2, h2): what layer_tail_bwd takes, and the layer's output."""
+    wo, bo, l1w, l1b, wi, bi, wo2, bo2, l2w, l2b = w
+    T, H, I = x.shape[0], c.hidden_size, c.intermediate_size
+    dev = x.device
+    a = _empty(T, H, x)
+    K.gemm(T, H, H, K.operand(cx, L.KCONTIG), K.operand(wo, L.KCONTIG), a, bias=bo)
+    h1 = _empty(T, H, x)
+    st1 = torch.empty(T, 2, device=dev)
+    K.bert_add_ln_fwd(a, x, l1w, l1b, c.layer_norm_eps, h1, st1, **drop1)
+    U = _empty(T, I, x)
+    G = _empty(T, I, x)
+    K.gemm(T, I, H, K.operand(h1, L.KCONTIG), K.operand(wi, L.KCONTIG), G, bias=bi,
+           epilogue=L.EPI_STORE_GELU, c_rows=K.operand(U, L.KCONTIG))
+    o = _empty(T, H, x)
+    K.gemm(T, H, I, K.operand(G, L.KCONTIG), K.operand(wo2, L.KCONTIG), o, bias=bo2)
+    h2 = _empty(T, H, x)
+    st2 = torch.empty(T, 2, device=dev)
+    K.bert_add_ln_fwd(o, h1, l2w, l2b, c.layer_norm_eps, h2, st2, **drop2)
+    return a, st1, h1, U, G, o, st2, h2
+
+
+def layer_tail_bwd(dh, x, cx, saved, w, g, drop1, drop2):
+    """Backward of layer_tail_fwd from the layer output's gradient dh: accumulates the ten parameter gradients
+    into g (zero-filled, in w's order) -> (dx: the residual path's share of the layer input's gradient, dcx)."""
+    a, st1, h1, U, G, o, st2 = saved
+    wo, _, l1w, _, wi, _, wo2, _, l2w, _ = w
+    T, H = x.shape
+    I = wi.shape[0]
+    dh1 = _empty(T, H, x)
+    do = _empty(T, H, x)
+    K.bert_add_ln_bwd(o, h1, l2w, st2, dh, dh1, do, g[8], g[9], **drop2)
+    dU = _empty(T, I, x)
+    K.gemm(T, I, H, K.operand(do, L.KCONTIG), K.operand(wo2, L.MNCONTIG), dU, epilogue=L.EPI_GELU_GRAD,
+           c_rows=K.operand(U, L.KCONTIG))
+    _proj_wgrad(do, K.operand(G, L.MNCONTIG), g[6], g[7], T)
+    K.gemm(T, H, I, K.operand(dU, L.KCONTIG), K.operand(wi, L.MNCONTIG), dh1, epilogue=L.EPI_ACCUM)
+    _proj_wgrad(dU, K.operand(h1, L.MNCONTIG), g[4], g[5], T)
+    dx = _empty(T, H, x)
+    da = _empty(T, H, x)
+    K.bert_add_ln_bwd(a, x, l1w, st1, dh1, dx, da, g[2], g[3], **drop1)
+    dcx = _empty(T, H, x)
+    K.gemm(T, H, H, K.operand(da, L.KCONTIG), K.operand(wo, L.MNCONTIG), dcx)
+    _proj_wgrad(da, K.operand(cx, L.MNCONTIG), g[0], g[1], T)
+    return dx, dcx
+
+
 class BertFn(torch.autograd.Function):
     """The BertModel forward over concatenated segments -> (last_hidden [T, H], pooled [S, H]).
     ``drop`` = list of per-site (seed, offset, rng, offset inside rng's range) or None (eval / p = 0)."""
@@ -228,20 +278,8 @@ class BertFn(torch.autograd.Function):
                     K.bert_attn_fwd(qkv[r0:r0 + n], heads, s.mask, s.nseq, s.L, cx[r0:r0 + n],
                                     ml[r0 * heads * 2:(r0 + n) * heads * 2], keep=kp,
                                     **dsite_seg(1 + 3 * li, p_a, r0))
-            a = _empty(T, H, word)
-            K.gemm(T, H, H, K.operand(cx, L.KCONTIG), K.operand(wo, L.KCONTIG), a, bias=bo)
-            h1 = _empty(T, H, word)
-            st1 = torch.empty(T, 2, device=dev)
-            K.bert_add_ln_fwd(a, x, l1w, l1b, c.layer_norm_eps, h1, st1, **dsite_seg(2 + 3 * li, p_h, 0))
-            U = _empty(T, I, word)
-            G = _empty(T, I, word)
-            K.gemm(T, I, H, K.operand(h1, L.KCONTIG), K.operand(wi, L.KCONTIG), G, bias=bi,
-                   epilogue=L.EPI_STORE_GELU, c_rows=K.operand(U, L.KCONTIG))
-            o = _empty(T, H, word)
-            K.gemm(T, H, I, K.operand(G, L.KCONTIG), K.operand(wo2, L.KCONTIG), o, bias=bo2)
-            h2 = _empty(T, H, word)
-            st2 = torch.empty(T, 2, device=dev)
-            K.bert_add_ln_fwd(o, h1, l2w, l2b, c.layer_norm_eps, h2, st2, **dsite_seg(3 + 3 * li, p_h, 0))
+            a, st1, h1, U, G, o, st2, h2 = layer_tail_fwd(c, x, cx, w[6:], dsite_seg(2 + 3 * li, p_h, 0),
+                                                          dsite_seg(3 + 3 * li, p_h, 0))
             saved += [x, wqkv, qkv, cx, ml, a, st1, h1, U, G, o, st2]
             keeps_all.append(keeps)
             x = h2
@@ -304,21 +342,8 @@ class BertFn(torch.autograd.Function):
                 dwqkv, dbqkv, *grest = _zeros_views(dev, (3 * H, H), (3 * H,),
                                                     *[tuple(t.shape) for t in lp[li][6:]])
                 g = [dwqkv[:H], dbqkv[:H], dwqkv[H:2 * H], dbqkv[H:2 * H], dwqkv[2 * H:], dbqkv[2 * H:]] + grest
-            dh1 = _empty(T, H, word)
-            do = _empty(T, H, word)
-            K.bert_add_ln_bwd(o, h1, l2w, st2, dh, dh1, do, g[14], g[15], **dsite_seg(3 + 3 * li, p_h, 0))
-            dU = _empty(T, I, word)
-            K.gemm(T, I, H, K.operand(do, L.KCONTIG), K.operand(wo2, L.MNCONTIG), dU, epilogue=L.EPI_GELU_GRAD,
-                   c_rows=K.operand(U, L.KCONTIG))
-            _proj_wgrad(do, K.operand(G, L.MNCONTIG), g[12], g[13], T)
-            K.gemm(T, H, I, K.operand(dU, L.KCONTIG), K.operand(wi, L.MNCONTIG), dh1, epilogue=L.EPI_ACCUM)
-            _proj_wgrad(dU, K.operand(h1, L.MNCONTIG), g[10], g[11], T)
-            dx = _empty(T, H, word)
-            da = _empty(T, H, word)
-            K.bert_add_ln_bwd(a, x, l1w, st1, dh1, dx, da, g[8], g[9], **dsite_seg(2 + 3 * li, p_h, 0))
-            dcx = _empty(T, H, word)
-            K.gemm(T, H, H, K.operand(da, L.KCONTIG), K.operand(wo, L.MNCONTIG), dcx)
-            _proj_wgrad(da, K.operand(cx, L.MNCONTIG), g[6], g[7], T)
+            dx, dcx = layer_tail_bwd(dh, x, cx, (a, st1, h1, U, G, o, st2), lp[li][6:], g[6:],
+                                     dsite_seg(2 + 3 * li, p_h, 0), dsite_seg(3 + 3 * li, p_h, 0))
             if synth:
                 hv, a1, probs, w1, w2 = wqkv, qkv, ml, wq, wk
                 da1 = _empty(T, SL, word)

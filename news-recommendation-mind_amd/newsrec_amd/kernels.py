@@ -1375,6 +1375,95 @@ def synth_attn_bwd(hv, w1, w2, a1, probs, dctx, nseq, seq_len, D, da1, da2, dhv)
            dhv.stride(0), L.stream_ptr(hv))
 
 
+DEB_MAX_L = 64
+DEB_MAX_HEADS = 1024
+DEB_INTERLEAVED = (192, 0, 64, 128)       # DeBERTa's in_proj: head h owns columns [192 h, 192 h + 192) as q | k | v
+
+
+def deb_blocked(heads):
+    """(hstride, qoff, koff, voff) of a blocked [q of every head | k | v] projection."""
+    return 64, 0, 64 * heads, 128 * heads
+
+
+def _deb_check(qkv, layout, pk, pq, mask, nseq, seq_len, heads, p_drop, who):
+    if nseq < 0 or not 1 <= seq_len <= DEB_MAX_L or not 1 <= heads <= DEB_MAX_HEADS or nseq * heads > 0x7fffffff:
+        raise L.HipError("%s: needs nseq >= 0, 1 <= L <= %d, 1 <= heads <= %d and nseq * heads < 2^31 (got %d, "
+                         "%d, %d)" % (who, DEB_MAX_L, DEB_MAX_HEADS, nseq, seq_len, heads))
+    hstride, qoff, koff, voff = (int(v) for v in layout)
+    offs = (qoff, koff, voff)
+    if hstride % 4 or hstride < 64 or any(o % 4 or o < 0 for o in offs) or \
+            any(abs(a - b) < 64 for a, b in ((qoff, koff), (qoff, voff), (koff, voff))):
+        raise L.HipError("%s: hstride and the q / k / v offsets must be multiples of 4, hstride >= 64, the offsets "
+                         ">= 0 and 64 or more apart (got %r)" % (who, (hstride,) + offs))
+    if not 0.0 <= p_drop < 1.0:
+        raise L.HipError("%s: 0 <= p_drop < 1 required" % who)
+    width = (heads - 1) * hstride + max(offs) + 64
+    _f32(qkv, pk, pq)
+    _al(qkv, who + " qkv")
+    _rows_ok(qkv, nseq * seq_len, width, "qkv")
+    if pk.stride(0) != pq.stride(0):
+        raise L.HipError("%s: pk and pq must share one leading dimension" % who)
+    for t, n in ((pk, "pk"), (pq, "pq")):
+        _al(t, who + " " + n)
+        _rows_ok(t, 2 * seq_len, 64 * heads, n)
+    mp, mdt = mask_arg(mask, nseq * seq_len)
+    return (hstride, qoff, koff, voff), width, mp, mdt
+
+
+def deb_attn_bwd_workspace(nseq, seq_len, heads):
+    """Bytes of workspace nr_deb_attn_bwd needs (the per-workgroup partial sums of dpk / dpq)."""
+    n = L.load().nr_deb_attn_bwd_workspace(nseq, seq_len, heads)
+    if n < 0:
+        raise L.HipError("deb_attn_bwd_workspace: invalid argument (nseq %d, L %d, heads %d)" % (nseq, seq_len, heads))
+    return n
+
+
+def deb_attn_fwd(qkv, pk, pq, mask, nseq, seq_len, heads, probs, ctx, layout=DEB_INTERLEAVED, scale=None,
+                 p_drop=0.0, seed=0, offset=0, rng=None):
+    """nr_deb_attn_fwd: DeBERTa's disentangled attention core on a [T, >= width] q / k / v projection whose
+    head h sits at columns h * hstride + (qoff, koff, voff) (``layout``), with the position projections pk, pq
+    [2L, >= 64 heads]: probs (flat, nseq*heads*L*L floats: after the mask, before the dropout) and ctx
+    [T, >= 64 heads]."""
+    lay, _, mp, mdt = _deb_check(qkv, layout, pk, pq, mask, nseq, seq_len, heads, p_drop, "deb_attn_fwd")
+    _f32(ctx, probs)
+    _al(ctx, "deb_attn_fwd ctx")
+    _rows_ok(ctx, nseq * seq_len, 64 * heads, "ctx")
+    if not probs.is_contiguous() or probs.numel() < nseq * heads * seq_len * seq_len:
+        raise L.HipError("deb_attn_fwd: probs needs nseq*heads*L*L contiguous floats")
+    scale = 1.0 / float(3 * 64) ** 0.5 if scale is None else float(scale)
+    p, s, o, r = _drop(p_drop, seed, offset, rng)
+    L.call("nr_deb_attn_fwd", L.ptr(qkv), qkv.stride(0), *lay, L.ptr(pk), L.ptr(pq), pk.stride(0), mp, mdt, nseq,
+           seq_len, heads, scale, p, s, o, r, L.ptr(probs), L.ptr(ctx), ctx.stride(0), L.stream_ptr(qkv))
+
+
+def deb_attn_bwd(qkv, pk, pq, mask, nseq, seq_len, heads, probs, dctx, dqkv, dpk, dpq, layout=DEB_INTERLEAVED,
+                 scale=None, p_drop=0.0, seed=0, offset=0, rng=None, work=None):
+    """nr_deb_attn_bwd: dctx [T, >= 64 heads] -> dq, dk, dv at qkv's columns of dqkv (every element of the
+    three blocks stored) and dpk, dpq [2L, >= 64 heads] summed over the titles (row 0 stored as 0).  ``work``:
+    float32 workspace of deb_attn_bwd_workspace bytes (None: allocated here)."""
+    lay, width, mp, mdt = _deb_check(qkv, layout, pk, pq, mask, nseq, seq_len, heads, p_drop, "deb_attn_bwd")
+    _f32(probs, dctx, dqkv, dpk, dpq, work)
+    T = nseq * seq_len
+    for t, n, rows, w in ((dctx, "dctx", T, 64 * heads), (dqkv, "dqkv", T, width),
+                          (dpk, "dpk", 2 * seq_len, 64 * heads), (dpq, "dpq", 2 * seq_len, 64 * heads)):
+        _al(t, "deb_attn_bwd " + n)
+        _rows_ok(t, rows, w, n)
+    if dpk.stride(0) != dpq.stride(0):
+        raise L.HipError("deb_attn_bwd: dpk and dpq must share one leading dimension")
+    if not probs.is_contiguous() or probs.numel() < T * heads * seq_len:
+        raise L.HipError("deb_attn_bwd: probs needs nseq*heads*L*L contiguous floats")
+    nbytes = deb_attn_bwd_workspace(nseq, seq_len, heads)
+    if work is None:
+        work = torch.empty(max(4, nbytes // 4), device=qkv.device, dtype=torch.float32)
+    elif not work.is_contiguous() or work.numel() * 4 < nbytes or work.data_ptr() % 16:
+        raise L.HipError("deb_attn_bwd: work needs %d contiguous 16-B aligned bytes" % nbytes)
+    scale = 1.0 / float(3 * 64) ** 0.5 if scale is None else float(scale)
+    p, s, o, r = _drop(p_drop, seed, offset, rng)
+    L.call("nr_deb_attn_bwd", L.ptr(qkv), qkv.stride(0), *lay, L.ptr(pk), L.ptr(pq), pk.stride(0), mp, mdt, nseq,
+           seq_len, heads, scale, p, s, o, r, L.ptr(probs), L.ptr(dctx), dctx.stride(0), L.ptr(dqkv), dqkv.stride(0),
+           L.ptr(dpk), L.ptr(dpq), dpk.stride(0), L.ptr(work), work.numel() * 4, L.stream_ptr(qkv))
+
+
 def tanh_bwd(y, dy, dx):
     _f32(y, dy, dx)
     rows, cols = y.shape

@@ -23,7 +23,7 @@ class ManagerConfig:
         self.encoderN = encoderN; self.encoderU = encoderU
         self.user_num = USER_NUM[scale] if user_num is None else user_num
         self.lr = lr; self.bert_lr = bert_lr
-        self.bert = bert      # the PLM tower (-b): "bert" or "synthesizer"
+        self.bert = bert      # the PLM tower (-b): "bert", "synthesizer", "deberta" or "newsbert"
 
     def get_user_num(self):
         return self.user_num

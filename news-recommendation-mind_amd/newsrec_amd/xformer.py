@@ -10,13 +10,23 @@ synthesizer in place of every layer's self-attention (``BertConfig(attention_typ
 of exactly ``manager.signal_length`` tokens).  ``XFormer`` refuses it: the reference builds none there, and
 its 501-token user sequence has no signal_length.
 
-Out of scope: the reformer / longformer / bigbird / deberta / funnel / distill /
-newsbert variants (XFormer.py:19-41, PLM.py:20-78).
+``PLM`` also takes ``manager.bert == "deberta"`` (PLM.py:19-28): ``deberta.DebertaModel`` (transformers'
+DebertaModel as microsoft/deberta-base configures it, disentangled attention on nr_deb_attn_*) for titles of
+at most 64 tokens, with the reference's own pooler ``self.pooler = Sequential(Linear, GELU)`` on the CLS rows
+of ``last_hidden_state`` (a DebertaModel has no pooler of its own).  ``XFormer`` refuses it: the reference's
+XFormer reads ``.pooler_output`` (XFormer.py:73,94), which a DebertaModel does not return.
+
+``manager.bert == "newsbert"`` (PLM.py:59-64) is BERT cut to its first four layers, pooler included:
+``BertConfig(num_hidden_layers=4)``.
+
+Out of scope: the reformer / longformer / bigbird / funnel / distill variants
+(XFormer.py:19-41, PLM.py:20-78), and deberta under XFormer.
 """
 import torch
 from torch import nn
 
 from .bert import BertConfig, BertModel
+from .deberta import ClsGeluPoolFn, DebertaConfig, DebertaModel
 from .twotower import TwoTowerBaseModel
 
 # Manager.get_max_length_for_truncating (utils/Manager.py:1013-1027), "bert" entry
@@ -30,8 +40,14 @@ def _bert_for(manager, bert, bert_config, towers=("bert",)):
                                   % (" / ".join(repr(t) for t in towers), " is" if len(towers) == 1 else "s are", name))
     if bert is not None:
         return bert
+    if name == "deberta":             # PLM.py:19-28: microsoft/deberta-base's architecture at bert_dim
+        if bert_config is None:
+            bert_config = DebertaConfig(hidden_size=manager.bert_dim, num_attention_heads=manager.bert_dim // 64)
+        return DebertaModel(bert_config)
     if bert_config is None:
         kw = {}
+        if name == "newsbert":        # PLM.py:59-64: BERT cut to its first four layers
+            kw = dict(num_hidden_layers=4)
         if name == "synthesizer":     # PLM.py:37-47: BERT-base with Synthesizer.py's self-attention in every layer
             kw = dict(attention_type="synthesizer", signal_length=manager.signal_length)
         bert_config = BertConfig(hidden_size=manager.bert_dim, num_attention_heads=manager.bert_dim // 64, **kw)
@@ -112,7 +128,10 @@ class PLM(TwoTowerBaseModel):
         ub = _user_bias(manager)
         if ub is not None:
             self.userBias = ub
-        self.bert = _bert_for(manager, bert, bert_config, towers=("bert", "synthesizer"))
+        self.bert = _bert_for(manager, bert, bert_config, towers=("bert", "synthesizer", "deberta", "newsbert"))
+        if getattr(manager, "bert", "bert") == "deberta":
+            # PLM.py:26-28: DebertaModel has no pooler; "pooler.*" takes the base lr (its name has no "bert")
+            self.pooler = nn.Sequential(nn.Linear(manager.bert_dim, manager.bert_dim), nn.GELU())
         manager.name = "__".join(["plm", getattr(manager, "bert", "bert"), manager.encoderU])
         self.name = manager.name
 
@@ -125,10 +144,17 @@ class PLM(TwoTowerBaseModel):
         m = x[key + "_attn_mask"].to(dev, non_blocking=True)
         return t.reshape(-1, t.shape[-1]), m.reshape(-1, t.shape[-1])
 
+    def _pooled(self, out):
+        """The title vectors of one BERT output: its pooler output, or for DeBERTa PLM's own pooler over the CLS
+        rows of last_hidden_state (PLM.py:102-106)."""
+        if hasattr(self, "pooler"):
+            return ClsGeluPoolFn.apply(out.last_hidden_state, self.pooler[0].weight, self.pooler[0].bias)
+        return out.pooler_output
+
     def encode_news(self, x):
         """PLM.py:89-104."""
         B = x["cdd_encoded_index"].shape[0]
-        return self.bert(*self._titles(x, "cdd")).pooler_output.view(B, -1, self.hidden_dim)
+        return self._pooled(self.bert(*self._titles(x, "cdd"))).view(B, -1, self.hidden_dim)
 
     def _user(self, his, x):
         dev = his.device
@@ -143,7 +169,7 @@ class PLM(TwoTowerBaseModel):
         if self.news_reprs is not None:
             his = self.news_reprs(x["his_id"].to(self._dev()))
         else:
-            his = self.bert(*self._titles(x, "his")).pooler_output.view(B, -1, self.hidden_dim)
+            his = self._pooled(self.bert(*self._titles(x, "his"))).view(B, -1, self.hidden_dim)
         return self._user(his, x), None
 
     def _encode_both(self, x):
@@ -154,7 +180,7 @@ class PLM(TwoTowerBaseModel):
         ht, hm = self._titles(x, "his")
         # candidates and history share L: one segment, one pass
         out = self.bert.encode_segments([(torch.cat([ct, ht], 0), torch.cat([cm, hm], 0))])[0]
-        pooled = out.pooler_output
+        pooled = self._pooled(out)
         cdd = pooled[:B * C].view(B, C, self.hidden_dim)
         his = pooled[B * C:].view(B, -1, self.hidden_dim)
         return cdd, self._user(his, x), None
